@@ -36,6 +36,11 @@ configs[1]: 10 000 x 20 000, stages A + B, unbalanced and balanced kNN); their k
 own Cython kernel where oracle/_ref travelled with the snapshot (`kind: "reference"`; built from /root/reference in the build
 container by oracle/build_ref.py), else by the oracle restatement (`kind: "port"`, oracle/libvelocyto_oracle.so + oracle.py);
 `parity` says how far the HIP path is from the restatement on that same sub-problem in all three modes.
+
+A plain run does what the headline needs and no more: set up, warm up, time the --steps steps, print the line (`stages` and `roofline`
+come from the HIP events of those steps).  `--full` adds everything else above: `telemetry`, the measured shader clock in `roofline`,
+`precision_modes` and `extra` (unless --no-extra), `cpu_baseline` (unless --no-cpu-baseline).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs); with the same arguments the inputs are the same from run to run.
 """
 import argparse
 import json
@@ -113,7 +118,13 @@ def parse():
                     help="N > 1: how ranks obtain the rows of e = Sx_sz their neighbour lists reference")
     ap.add_argument("--no-overlap", dest="overlap", action="store_false",
                     help="N > 1 with the halo exchange: do not split stage D into interior cells (run while the halo moves) and the rest")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: SMI telemetry around the timed steps, the shader clock under stage D "
+                         "(extra, untimed steps), the precision modes and extra lines (unless --no-extra), the CPU baseline and its parity "
+                         "block (unless --no-cpu-baseline).  Off: set up, warm up, time the steps, print the line")
     ap.add_argument("--dump", default=None, help="rank 0 saves gamma and the gathered correlation rows of the last step to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (see dump_outputs), at most 64 MB in all")
     ap.add_argument("--generator", choices=["survey", "bench"], default="survey",
                     help="synthetic dataset: 'survey' (default from round 6) = SURVEY.md 8(d)'s - numpy PCG64(20180808 + cfg#), 12 clusters on a branching latent "
                          "time, the splicing ODE's closed form; 'bench' = the device-side generator rounds 1-5 were timed on (one branch point, seed 20180811)")
@@ -122,7 +133,12 @@ def parse():
                          "8-cell groups share more neighbours: 97.3 vs 98.6 ms)")
     ap.add_argument("--order", choices=["natural", "embedding"], default="embedding",
                     help="schedule order of the cells in stage D (results are order-independent)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.workload != "cfg3":
+        ap.error("--dump-outputs is for the default workload (cfg3)")
+    return a
 
 
 def synth_counts(C, G, P, dev, seed=20180811):
@@ -550,6 +566,17 @@ def hip_subproblem(pipe, args, Cs, ixs, dtype, rules):
     return Sx, gamma, corr
 
 
+def host_cores():
+    """The CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the environment sets it (on a shared host
+    os.cpu_count() counts the whole machine, not the share of it this run was given).  Sizes every host thread pool of the CPU baseline."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        omp = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        omp = 0
+    return max(1, min(n, omp) if omp > 0 else n)
+
+
 def _host_genes_major(work, name, M, block=1500):
     """The (genes, cells) fp64 form of a cells-major device matrix as <work>/<name>.npy, written gene block by gene block through a pinned
     buffer (no second host copy).  Returns the memory map."""
@@ -569,16 +596,16 @@ def cpu_full_width(pipe, args):
     neighbour lists are the run's own, so every gather e[j * cols + i] has the stride of all 50 000 columns.
       * the reference's OWN kernel (oracle/_ref): it has no cell range, so it is started over all columns and the rows it has finished are
         counted at two instants before it is stopped (oracle.reference_coldeltacor_rate), at the reference's thread rule cpu_count() / 2
-        (estimation.py:27-28);
-      * the restatement (oracle/velocyto_oracle.c, the same loop order and scratch) on the first cells of the run, at cpu_count() / 2 and at
-        all cores."""
+        (estimation.py:27-28) applied to the cores this run may use (host_cores);
+      * the restatement (oracle/velocyto_oracle.c, the same loop order and scratch) on the first cells of the run, at half and at all of
+        those cores."""
     import shutil
     import tempfile
     import oracle
     import psutil
     ops = pipe.ops
     C, G, nr = args.cells, args.genes, pipe.nrndm
-    cores = os.cpu_count() or 1
+    cores = host_cores()
     need = 2 * C * G * 8 + cores * G * nr * 8 * 2.2 + (8 << 30)          # e, d, the kernels' scratch (A and A - mean per thread), slack
     avail = psutil.virtual_memory().available
     if not os.path.isdir("/dev/shm") or avail < need or shutil.disk_usage("/dev/shm").free < 2 * C * G * 8 + (4 << 30):
@@ -616,7 +643,7 @@ def cpu_full_width(pipe, args):
             try:
                 out["reference_kernel"] = {**oracle.reference_coldeltacor_rate(work, ixs, "sqrt", 1e-10, threads=half, t_first=5.0, t_second=17.0),
                                            "kernel": "velocyto/speedboosted.pyx _colDeltaCorSqrtpartial (oracle/_ref), all columns started, rows finished between two readings",
-                                           "thread_rule": "cpu_count() / 2 (estimation.py:27-28)"}
+                                           "thread_rule": "cpu_count() / 2 (estimation.py:27-28) of the cores this run may use"}
             except Exception as ex:                                          # noqa: BLE001
                 out["reference_kernel"] = {"error": f"{type(ex).__name__}: {ex}"[:300]}
         else:
@@ -641,7 +668,7 @@ def cpu_baseline(pipe, args):
     ops = pipe.ops
     Cs = min(args.cpu_cells, args.cells)
     G = args.genes
-    cores = os.cpu_count() or 1
+    cores = host_cores()
     half = max(1, cores // 2)
     cnt = lambda cm: cm.as_int32(0, Cs).double()
     S = (cnt(pipe.cS) * pipe.fS[:Cs, None]).cpu().numpy().T.copy()     # S_sz in the reference's (G, Cs) layout
@@ -725,7 +752,7 @@ def cpu_baseline(pipe, args):
     if "cells_per_s" in rk:
         dps, kind, th = rk["cells_per_s"], "reference", rk["threads"]
         what = (f"stage D by the reference's own Cython kernel over the run's full {args.cells}-column fp64 matrices (stride {args.cells} cells = {args.cells * 8} B between "
-                f"the genes of a cell) with the run's neighbour lists, {th} threads = cpu_count() / 2 (estimation.py:27-28): {rk['rows_second'] - rk['rows_first']} cells finished "
+                f"the genes of a cell) with the run's neighbour lists, {th} threads = half the cores this run may use (estimation.py:27-28): {rk['rows_second'] - rk['rows_first']} cells finished "
                 f"between {rk['t_first']:.1f} s and {rk['t_second']:.1f} s of a run over all columns, then stopped")
     elif rs:
         best = max(rs.values(), key=lambda r: r["cells_per_s"])
@@ -831,6 +858,50 @@ def dominant_roofline(a, pipe, d_ms, dtype):
     return roof
 
 
+OUTPUT_SAMPLE_SEED = 20180808          # the rows of the sampled outputs: same arguments, same rows
+OUTPUT_BYTES = {"corr": 32 << 20, "Sx": 8 << 20, "Ux": 8 << 20}      # per sampled array: with gamma and the row lists well under 64 MB
+
+
+def _sample_rows(n, row_bytes, budget):
+    """All n rows when they fit the budget, else a fixed, seeded, sorted sample of as many as fit."""
+    m = max(1, int(budget // row_bytes))
+    if m >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(OUTPUT_SAMPLE_SEED).choice(n, m, replace=False))
+
+
+def dump_outputs(a, pipe):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in the dtype the path returns it (corr, Sx, Ux in
+    the run's arithmetic: float64 for --dtype f64, float32 for f32; gamma float32), so that two builds run with the same arguments (hence
+    the same inputs) can be compared output for output:
+      gamma  (genes,)              fit_slope's per-gene slopes, every gene
+      corr   (rows, nrndm)         colDeltaCorSqrtpartial's compact correlations of the cells in corr_rows
+      Sx, Ux (rows, genes)         knn_imputation's pooled spliced / unspliced values of the cells in pool_rows (rank 0's own cells at N > 1)
+      corr_rows, pool_rows         the cell numbers of those rows (float64): all cells where the array fits its share of the 64 MB
+                                   (OUTPUT_BYTES), else a fixed, seeded sample.
+    Returns the record of what was written, for the JSON line."""
+    out_dir = a.dump_outputs
+    os.makedirs(out_dir, exist_ok=True)
+    G = a.genes
+    es = 8 if pipe.dtype == torch.float64 else 4
+    corr_rows = _sample_rows(pipe.corr.shape[0], pipe.corr.shape[1] * es, OUTPUT_BYTES["corr"])
+    pool_rows = _sample_rows(pipe.c1 - pipe.c0, G * es, OUTPUT_BYTES["Sx"])
+    sel = lambda rows: torch.from_numpy(rows).to(pipe.dev)
+    arrays = {"gamma": pipe.last_gamma,
+              "corr": pipe.corr.index_select(0, sel(corr_rows)),
+              "Sx": pipe.Sx_loc.t[:, :G].index_select(0, sel(pool_rows)),
+              "Ux": pipe.Ux_loc.t[:, :G].index_select(0, sel(pool_rows))}
+    rec = {}
+    for name, t in arrays.items():
+        x = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        rec[name] = {"shape": list(x.shape), "dtype": str(x.dtype)}
+    for name, rows in (("corr_rows", corr_rows), ("pool_rows", pool_rows)):
+        np.save(os.path.join(out_dir, name + ".npy"), rows.astype(np.float64))
+        rec[name] = {"shape": [int(rows.size)], "dtype": "float64"}
+    return {"dir": out_dir, "arrays": rec, "sample_seed": OUTPUT_SAMPLE_SEED}
+
+
 def run(a, rank, local_rank, world):
     if os.environ.get("VCY_SINGLE_DEVICE", "0") == "1":     # multi-process test on a one-GPU box: every rank on device 0, gloo
         local_rank = 0
@@ -879,20 +950,22 @@ def run(a, rank, local_rank, world):
         if dist.is_initialized():
             dist.barrier()
         torch.cuda.synchronize()
-    smi_before = smi_sample() if rank == 0 else None
+    smi_before = smi_sample() if (rank == 0 and a.full) else None
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         pipe.step(timed=True)
     barrier()
     dt = time.perf_counter() - t0
-    smi_after = smi_sample() if rank == 0 else None
+    smi_after = smi_sample() if (rank == 0 and a.full) else None
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     ms_per_step = dt / a.steps * 1e3
-    pipe.probe_clock()                                      # untimed: the shader clock under stage D, for roofline.effective_clock_ghz
+    outputs = dump_outputs(a, pipe) if (rank == 0 and a.dump_outputs) else None      # the last timed step's results, before anything runs again
+    if a.full:
+        pipe.probe_clock()                                  # untimed: the shader clock under stage D, for roofline.effective_clock_ghz
     # every rank's own view of the pass (stage times, shard and halo sizes) -> rank 0, for config.parallelism_detail
     per_rank = None
     if dist.is_initialized() and pipe.collect:
@@ -970,15 +1043,18 @@ def run(a, rank, local_rank, world):
                        "velocity_chain": "folded into the staging of d[c] in the stage-D kernel" if a.fuse else "k_velocity_chain (dmat materialised)",
                        "cell_order_D": a.order + (f" ({a.curve} curve)" if a.order == "embedding" else "")},
             "roofline": roof, "stages": stages,
-            "telemetry": {"smi_before_timed_steps": smi_before, "smi_after_timed_steps": smi_after,
-                          "note": "rocm-smi of GPU 0 (socket power, temperatures, clocks as the SMI reports them) sampled on the host right before and right "
-                                  "after the timed steps; the shader clock UNDER stage D is roofline.effective_clock (per XCD: per_xcd_mean / per_xcd_min)"},
         }
-        if world == 1 and not a.no_extra:
+        if outputs is not None:
+            res["outputs"] = outputs
+        if a.full:
+            res["telemetry"] = {"smi_before_timed_steps": smi_before, "smi_after_timed_steps": smi_after,
+                                "note": "rocm-smi of GPU 0 (socket power, temperatures, clocks as the SMI reports them) sampled on the host right before and right "
+                                        "after the timed steps; the shader clock UNDER stage D is roofline.effective_clock (per XCD: per_xcd_mean / per_xcd_min)"}
+        if a.full and world == 1 and not a.no_extra:
             res["precision_modes"], res["extra"] = extra_lines(a, dev, pipe, res)
             # the key numbers of the extra lines as scalars of `config` (the driver's record keeps scalars)
             res["config"].update(extra_scalars(res["extra"], res["precision_modes"]))
-        if not a.no_cpu_baseline and world == 1:     # reported on rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:     # reported on rank 0 at N = 1 only
             res["cpu_baseline"] = cpu_baseline(pipe, a)
     finish(res, rank)
 

@@ -22,7 +22,7 @@ def test_bench_line_structure():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--cells", "6000", "--genes", "2048", "--n-neighbors", "100", "--k", "12", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--full", "--cells", "6000", "--genes", "2048", "--n-neighbors", "100", "--k", "12", "--steps", "2", "--warmup", "1",
            "--cpu-cells", "128", "--extra-budget-s", "300"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -95,3 +95,35 @@ def test_bench_line_structure():
     assert cb["parity"]["f64"]["max_abs_dcorr"] < 1e-8 and cb["parity"]["f32_nopsc"]["max_abs_dcorr"] < 5e-5
     same = cb["parity"]["f64"]["stage_D_on_identical_inputs"]                       # stage D alone on the HIP path's own pooled matrices
     assert same["max_abs_dcorr"] < 1e-10 and same["nan_pattern_equal"]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the line holds the headline of exactly --steps timed steps and nothing measured beside it; --dump-outputs writes
+    the last step's results as float .npy files under 64 MB, and two runs with the same arguments write the same results."""
+    import numpy as np
+    from velocyto_amd import ops
+    ops.require_gpu()
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+
+    def go(name):
+        out = tmp_path / name
+        cmd = [sys.executable, "bench.py", "--cells", "6000", "--genes", "2048", "--n-neighbors", "100", "--k", "12", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = json.loads([l for l in r.stdout.strip().splitlines() if l.strip()][-1])
+        return j, {f.name[:-4]: np.load(f) for f in out.glob("*.npy")}
+    j, a = go("one")
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "f64" and j["unit"] == "cells/s" and j["higher_is_better"] is True
+    assert abs(j["value"] - 6000 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"] and "cells/sec" in j["metric"]
+    assert not any(k in j for k in ("extra", "precision_modes", "cpu_baseline", "telemetry")) and "effective_clock" not in j["roofline"]
+    assert set(a) == {"gamma", "corr", "Sx", "Ux", "corr_rows", "pool_rows"} and set(j["outputs"]["arrays"]) == set(a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64e6
+    assert a["gamma"].shape == (2048,) and a["corr"].shape == (6000, j["config"]["nrndm"]) and a["Sx"].shape[1] == a["Ux"].shape[1] == 2048
+    assert np.array_equal(a["corr_rows"], np.arange(6000)) and np.isfinite(a["corr"]).mean() > 0.99
+    _, b = go("two")
+    for k in a:
+        assert np.array_equal(np.isnan(a[k]), np.isnan(b[k])), k
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-12, atol=1e-13, err_msg=k)

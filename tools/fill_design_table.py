@@ -9,7 +9,7 @@ tel = d["telemetry"]
 pw = lambda t: t.get("Current Socket Graphics Package Power (W)", "?")
 tj = lambda t: t.get("Temperature (Sensor junction) (C)", "?")
 tab = f"""<!-- R6_TABLE_BEGIN (tools/fill_design_table.py) -->
-| line (one box, `python bench.py --gpus 1 --steps 20 --warmup 5`; `profiles/r06_bench_line.json`) | value |
+| line (one box, `python bench.py --full --gpus 1 --steps 20 --warmup 5`; `profiles/r06_bench_line.json`) | value |
 |---|---|
 | **headline: cells/s through A → B → (C) → D, f64, uint16 layers, survey dataset** | **{d['value']/1e3:.1f} k cells/s** ({d['ms_per_step']:.1f} ms per pass) |
 | the same on the dataset of rounds 1-5 (`--generator bench`, `r06_bench_line_generator_bench.json`; round 5's builder line: 197.6-202 k) | {g['value']/1e3:.1f} k cells/s (stage D {g['config']['stage_ms']['D_coldeltacor']:.1f} ms) |
@@ -37,7 +37,7 @@ s = open(p).read()
 if "<!-- R6_TABLE_BEGIN" in s:
     s = re.sub(r"<!-- R6_TABLE_BEGIN.*?<!-- R6_TABLE_END -->", lambda m: tab, s, flags=re.S)
 else:
-    a = s.index("| line (one box, `python bench.py --gpus 1 --steps 20 --warmup 5`")
+    a = s.index("| line (one box, `python bench.py --full --gpus 1 --steps 20 --warmup 5`")
     b = s.index("## 5. Parity")
     s = s[:a] + tab + "\n\n" + s[b:]
 open(p, "w").write(s)

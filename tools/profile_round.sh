@@ -22,5 +22,5 @@ find $R/gpurun_out -name "*.db" -delete 2>/dev/null
 cd $R
 python tools/summarize_profiles.py $T "${2:-}" > gpurun_out/${T}_summarize.log 2>&1     # writes profiles/<tag>_cdc_counters.json on the box, so that
 cp profiles/${T}_* gpurun_out/ 2>/dev/null                                                # the bench line below is computed from THIS build's counters
-python bench.py 2>&1 | tail -1 > gpurun_out/${T}_bench_line.json
-cut -c1-300 gpurun_out/${T}_bench_line.json
+python bench.py --full 2>&1 | tail -1 > profiles/${T}_bench_line.json      # the full line, computed from those counters
+cut -c1-300 profiles/${T}_bench_line.json

@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 L=velocyto.py_amd/libvelocyto_hip.so
 cp $L /tmp/prod.so
-X="--no-extra"; [ -n "$EXTRA" ] && X=""
+X=""; [ -n "$EXTRA" ] && X="--full"
 one() { python bench.py --no-cpu-baseline $X --steps ${STEPS:-3} --warmup 1 2>&1 | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); x=d.get('extra',{})
 print('$1', round(d['value']), {k: round(v, 2) for k, v in d['config']['stage_ms'].items()}, 'dual', x.get('randomised_control',{}).get('D_dual_ms'), 'f64', x.get('f64',{}).get('ms_per_step'))"; }
