@@ -330,6 +330,30 @@ int vcy_fit_weighted(const void *Y, const void *X, int weight_mode, const void *
                      const double *q_fixed, float *gamma, float *q, float *R2, void *workspace, int64_t C,
                      int64_t G, int64_t ld, int dtype, vcy_stream stream);
 
+/* Two-step form of vcy_fit_weighted for cell-sharded runs (analysis.py:1223-1257 over the cells of all ranks): the moments of a
+ * block of cells, (10, G) fp64 [Sx Sy Sxx Sxy Syy | Sw Swx Swy Swxx Swxy] (x = X, y = Y, w the weight of weight_mode), summed
+ * in the same fixed block order as vcy_fit_weighted; the caller adds the blocks' moments (an all-reduce), then solves them with
+ * vcy_fit_weighted_from_moments over n_cells = the number of cells the sum covers.  Arguments as vcy_fit_weighted's;
+ * workspace: vcy_fit_workspace_bytes(G).  vcy_fit_weighted is the composition of the two on one block.                    */
+int vcy_fit_weighted_moments(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
+                             const double *scale_a, const double *scale_b, const double *down, const double *up, double *moments,
+                             void *workspace, int64_t C, int64_t G, int64_t ld, int dtype, vcy_stream stream);
+int vcy_fit_weighted_from_moments(const double *moments, int64_t n_cells, int fit_offset, int box_q, double lo_gamma,
+                                  double up_gamma_default, const double *up_gamma, const double *q_fixed, float *gamma, float *q,
+                                  float *R2, int64_t G, vcy_stream stream);
+
+/* ---------------------------------------------------------------- gene-slice exchange of cell-sharded runs
+ * The per-gene percentiles of fit_gammas (analysis.py:1197-1206) and the per-gene shuffle of the randomised control
+ * (analysis.py:1540-1541) need every cell of a gene: a cells-sharded matrix goes to gene slices through one all-to-all each
+ * way, its blocks gene-major on the wire.  The N cells of a buffer form nseg segments seg[0] = 0 < ... < seg[nseg] = N (int64,
+ * device); element (cell c, gene g) of segment j sits at seg[j]*G + g*(seg[j+1]-seg[j]) + (c-seg[j]) - with one segment the
+ * gene-major (G, N) transpose.  pack reads the cells-major (rows, ld) matrix `src`, unpack writes the cells-major `dst` (its
+ * columns G..ld-1 are not written); row_map (int64 (N), device, or NULL = identity) is the matrix row of buffer cell c.     */
+int vcy_gene_slices_pack(const void *src, const int64_t *row_map, const int64_t *seg, int nseg, void *buf, int64_t N, int64_t G,
+                         int64_t ld, int dtype, vcy_stream stream);
+int vcy_gene_slices_unpack(const void *buf, const int64_t *row_map, const int64_t *seg, int nseg, void *dst, int64_t N, int64_t G,
+                           int64_t ld, int dtype, vcy_stream stream);
+
 /* ---------------------------------------------------------------- stage C: velocity chain
  * predict_U -> calculate_velocity -> calculate_shift -> extrapolate_cell_at_t and the
  * `dmat` transform of estimate_transition_prob, fused (analysis.py:1321-1439, 1538,
@@ -390,6 +414,11 @@ int vcy_delta_transform(const void *hi_dim, const void *delta_S, void *dmat, voi
 size_t vcy_permute_rows_nsign_workspace_bytes(int64_t C, int64_t G, int dtype);
 int vcy_permute_rows_nsign(const void *in, void *out, void *workspace_a, void *workspace_b, int64_t C, int64_t G, int64_t ld,
                            uint64_t seed, int dtype, vcy_stream stream);
+/* vcy_permute_rows_nsign on the columns of a GENE SLICE: column j is gene gene0 + j of the whole matrix and gets that gene's
+ * permutation and signs, so the slices of a matrix shuffled one by one equal the whole matrix shuffled (analysis.py:1540-1541
+ * in a cell-sharded run, where a rank holds genes [gene0, gene0 + G) of every cell).  gene0 = 0 is vcy_permute_rows_nsign.   */
+int vcy_permute_rows_nsign_genes(const void *in, void *out, void *workspace_a, void *workspace_b, int64_t C, int64_t G, int64_t ld,
+                                 int64_t gene0, uint64_t seed, int dtype, vcy_stream stream);
 /* np.fill_diagonal(corrcoef, 0) and corrcoef[isnan] = nan_to (analysis.py:1604-1612, 1666-1668) on
  * the compact (C_out, nrndm) form; nan_count (device int, may be NULL) counts the NaNs seen.  */
 int vcy_corr_fixup(void *vals, const int32_t *ixs, int64_t cell0, int64_t C_out, int64_t nrndm, int zero_self, int fix_nan,
@@ -447,6 +476,16 @@ int vcy_prepare_markov_factored(const int64_t *indptr, const int32_t *indices, c
 int vcy_diffuse_step_factored(const double *x, double *y, double *accum, const int64_t *colptr, const int32_t *rowidx, const double *scsc,
                               const double *tot, const double *kw, const void *es, int edim, double sigma_W, void *workspace, int64_t n,
                               int prepared, int compute_dtype, vcy_stream stream);
+/* One step of the same chain for the targets at positions [t0, t1) only (cell-sharded run_markov, analysis.py:1865-1887: a rank
+ * owns a target range, the length-n state x is all-gathered before every step).  Position = cell number, or - for the culled
+ * transform (boxes != NULL; es = es_sorted, rank, order, cut as for vcy_diffuse_step_factored_culled) - the cell's place in the
+ * sorted order, i.e. the targets are cells order[t0 .. t1-1].  y[j] (and accum[j] += y[j]) is written for those cells only, bit for
+ * bit what the full step writes there; v = x / tot is always computed from x (no `prepared`).  workspace:
+ * vcy_markov_factored_workspace_bytes(n).                                                                                    */
+int vcy_diffuse_step_factored_rows(const double *x, double *y, double *accum, const int64_t *colptr, const int32_t *rowidx,
+                                   const double *scsc, const double *tot, const double *kw, const void *es, const int32_t *rank,
+                                   const int32_t *order, const void *boxes, int edim, double sigma_W, double cut, void *workspace,
+                                   int64_t n, int64_t t0, int64_t t1, int compute_dtype, vcy_stream stream);
 
 /* The factored step when K_W is narrow against the extent of the embedding (prepare_markov is usually given a sigma_W of a grid step,
  * analysis.py:1818-1863): terms below 2^-cut of their weight are left out of the Gauss transform.  The caller sorts the cells along a

@@ -75,6 +75,8 @@ SIGNATURES = {
     "vcy_diffuse_step_factored_culled": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_dbl, c_dbl, c_vp,
                                                  c_i64, c_int, c_int, c_vp]),
     "vcy_diffuse_step_factored": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_i64, c_int, c_int, c_vp]),
+    "vcy_diffuse_step_factored_rows": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_dbl, c_dbl, c_vp,
+                                               c_i64, c_i64, c_i64, c_int, c_vp]),
     "vcy_gram_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_int]),
     "vcy_col_means": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     "vcy_gram": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp]),
@@ -103,6 +105,11 @@ SIGNATURES = {
     "vcy_diffuse_step_csc": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "vcy_fit_weighted": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_dbl,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_fit_weighted_moments": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_fit_weighted_from_moments": (c_int, [c_vp, c_i64, c_int, c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "vcy_gene_slices_pack": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_gene_slices_unpack": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_permute_rows_nsign_genes": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.c_uint64, c_int, c_vp]),
     "vcy_lincomb": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_vp]),
     "vcy_velocity_chain": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                    c_dbl, c_dbl, c_dbl, c_int, c_int, c_int, c_dbl, c_int, c_vp]),

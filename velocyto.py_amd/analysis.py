@@ -846,17 +846,7 @@ class VelocytoLoom(PreprocessMixin):
             raise NotImplementedError(f"{direction} is not an implemented direction")
         embedding = np.asarray(self.embedding, dtype=np.float64)
         if cells_ixs is None:
-            # all cells: the CSR of transition_prob is the compact (C, n) layout itself, its transpose one device sort
-            tp, ixs = self._tp.double().contiguous(), self._tp_ixs.to(torch.int64).contiguous()
-            C, n = tp.shape
-            if direction == "forward":
-                indptr, indices, data = torch.arange(0, C * n + 1, n, device=tp.device), ixs.ravel(), tp.ravel()
-            else:
-                rows, cols = ixs.ravel(), torch.arange(C, device=tp.device).repeat_interleave(n)
-                order = torch.argsort(rows * C + cols)
-                indptr = torch.zeros(C + 1, dtype=torch.int64, device=tp.device)
-                indptr[1:] = torch.cumsum(torch.bincount(rows, minlength=C), 0)
-                indices, data = cols[order], tp.ravel()[order]
+            indptr, indices, data = markov_csr(self._tp, self._tp_ixs, direction)
         else:
             tp, ixs = self._tp.double().cpu().numpy(), self._tp_ixs.cpu().numpy().astype(np.int64)
             C, n = tp.shape
@@ -932,6 +922,20 @@ class VelocytoLoom(PreprocessMixin):
             self.raw_S, self.raw_U, self.raw_A = layers["spliced"], layers["unspliced"], layers.get("ambiguous")
             self.raw_initial_cell_size, self.raw_initial_Ucell_size = self.raw_S.sum(0), self.raw_U.sum(0)
             self.raw_ca, self.raw_ra = dict(ca), dict(ra)
+
+
+def markov_csr(tp: torch.Tensor, ixs: torch.Tensor, direction: str):
+    """prepare_markov's CSR of the transition probabilities of all cells (indptr, indices, data on the device): the compact (C, n)
+    neighbour-list layout itself for "forward", its transpose (one device sort) for "backwards"."""
+    tp, ixs = tp.double().contiguous(), ixs.to(torch.int64).contiguous()
+    C, n = tp.shape
+    if direction == "forward":
+        return torch.arange(0, C * n + 1, n, device=tp.device), ixs.ravel(), tp.ravel()
+    rows, cols = ixs.ravel(), torch.arange(C, device=tp.device).repeat_interleave(n)
+    order = torch.argsort(rows * C + cols)
+    indptr = torch.zeros(C + 1, dtype=torch.int64, device=tp.device)
+    indptr[1:] = torch.cumsum(torch.bincount(rows, minlength=C), 0)
+    return indptr, cols[order], tp.ravel()[order]
 
 
 def ixs_thatsort_a2b(a: np.ndarray, b: np.ndarray, check_content: bool = True) -> np.ndarray:

@@ -182,19 +182,14 @@ __device__ inline void box_wls2(double sw, double sx, double sy, double sxx, dou
 // fit_offset=0          : _fit1_slope_weighted (estimation.py:191-209) / fixperc_q branches: gamma in
 //                          [lo_gamma, up_gamma] with the offset fixed to q_fixed[g]
 // R2 (estimation.py:323-331, 355-363) is unweighted, -1e16 when non-finite.
-__global__ void k_fit_weighted_final(const double *__restrict__ part, int fit_offset, int box_q, double lo_gamma,
-                                     double up_gamma_default, const double *__restrict__ up_gamma, const double *__restrict__ q_fixed,
-                                     float *__restrict__ gamma, float *__restrict__ qout, float *__restrict__ R2, int C, int G)
+// The solve of one gene from its ten reduced moments over n cells (shared by the one-pass and the two-step forms below).
+__device__ __forceinline__ void fit_weighted_solve(const double *mo, double n, int g, int fit_offset, int box_q, double lo_gamma,
+                                                   double up_gamma_default, const double *__restrict__ up_gamma,
+                                                   const double *__restrict__ q_fixed, float *__restrict__ gamma, float *__restrict__ qout,
+                                                   float *__restrict__ R2)
 {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= G) return;
-    double mo[FIT_NMOM];
-    for (int k = 0; k < FIT_NMOM; ++k) mo[k] = 0;
-    for (int cb = 0; cb < FIT_CB; ++cb)
-        for (int k = 0; k < FIT_NMOM; ++k) mo[k] += part[((int64_t)cb * FIT_NMOM + k) * G + g];
     const double sx = mo[0], sy = mo[1], sxx = mo[2], sxy = mo[3], syy = mo[4];
     const double sw = mo[5], swx = mo[6], swy = mo[7], swxx = mo[8], swxy = mo[9];
-    const double n = (double)C;
     const double hi = up_gamma ? up_gamma[g] : up_gamma_default;
     double m, q;
     if (!(sxx > 0)) { m = NAN; q = 0.0; }
@@ -220,6 +215,47 @@ __global__ void k_fit_weighted_final(const double *__restrict__ part, int fit_of
         const double r2 = 1.0 - ssres / sstot;
         R2[g] = isfinite(r2) ? (float)r2 : -1e16f;
     }
+}
+
+// the per-block partials summed in block order, then solved
+__device__ __forceinline__ void fold_partials(const double *__restrict__ part, int G, int g, double *mo)
+{
+    for (int k = 0; k < FIT_NMOM; ++k) mo[k] = 0;
+    for (int cb = 0; cb < FIT_CB; ++cb)
+        for (int k = 0; k < FIT_NMOM; ++k) mo[k] += part[((int64_t)cb * FIT_NMOM + k) * G + g];
+}
+
+__global__ void k_fit_weighted_final(const double *__restrict__ part, int fit_offset, int box_q, double lo_gamma,
+                                     double up_gamma_default, const double *__restrict__ up_gamma, const double *__restrict__ q_fixed,
+                                     float *__restrict__ gamma, float *__restrict__ qout, float *__restrict__ R2, int C, int G)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    double mo[FIT_NMOM];
+    fold_partials(part, G, g, mo);
+    fit_weighted_solve(mo, (double)C, g, fit_offset, box_q, lo_gamma, up_gamma_default, up_gamma, q_fixed, gamma, qout, R2);
+}
+
+// two-step form (cell-sharded fits): the folded moments (FIT_NMOM, G) of a block of cells ...
+__global__ void k_fit_weighted_fold(const double *__restrict__ part, double *__restrict__ mom, int G)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    double mo[FIT_NMOM];
+    fold_partials(part, G, g, mo);
+    for (int k = 0; k < FIT_NMOM; ++k) mom[(int64_t)k * G + g] = mo[k];
+}
+
+// ... and the solve from moments summed over all blocks (n = the number of cells they cover)
+__global__ void k_fit_weighted_from_moments(const double *__restrict__ mom, double n, int fit_offset, int box_q, double lo_gamma,
+                                            double up_gamma_default, const double *__restrict__ up_gamma, const double *__restrict__ q_fixed,
+                                            float *__restrict__ gamma, float *__restrict__ qout, float *__restrict__ R2, int G)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    double mo[FIT_NMOM];
+    for (int k = 0; k < FIT_NMOM; ++k) mo[k] = mom[(int64_t)k * G + g];
+    fit_weighted_solve(mo, n, g, fit_offset, box_q, lo_gamma, up_gamma_default, up_gamma, q_fixed, gamma, qout, R2);
 }
 
 // ---------------------------------------------------------------- per-gene order statistics
@@ -593,20 +629,16 @@ extern "C" int vcy_fit_slope(const void *Y, const void *X, float *gamma, void *w
     return vcy_fit_slope_from_moments(mom, gamma, G, stream);
 }
 
-extern "C" int vcy_fit_weighted(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
-                                const double *scale_a, const double *scale_b, const double *down, const double *up,
-                                int fit_offset, int box_q, double lo_gamma, double up_gamma_default, const double *up_gamma,
-                                const double *q_fixed, float *gamma, float *q, float *R2, void *workspace, int64_t C, int64_t G,
-                                int64_t ld, int dtype, vcy_stream stream)
+static int fit_weighted_partials(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
+                                 const double *scale_a, const double *scale_b, const double *down, const double *up, void *workspace,
+                                 int64_t C, int64_t G, int64_t ld, int dtype, hipStream_t st)
 {
-    VCY_REQUIRE(Y && X && gamma && workspace, "fit_weighted: null pointer");
     VCY_REQUIRE(C > 0 && G > 0 && ld >= G, "fit_weighted: bad shape");
     VCY_REQUIRE(dtype == VCY_F32 || dtype == VCY_F64, "fit_weighted: bad dtype");
     VCY_REQUIRE(weight_mode >= 0 && weight_mode <= 2, "fit_weighted: bad weight_mode");
     VCY_REQUIRE(weight_mode != 0 || W, "fit_weighted: weight_mode 0 needs W");
     VCY_REQUIRE(weight_mode != 1 || (M && down && up), "fit_weighted: weight_mode 1 needs M, down, up");
     VCY_REQUIRE(weight_mode != 1 || ((scale_a == nullptr) == (scale_b == nullptr) && (scale_a == nullptr || M2)), "fit_weighted: scale_a/scale_b/M2 go together");
-    hipStream_t st = as_stream(stream);
     dim3 grid((unsigned)((G + 255) / 256), FIT_CB);
 #define VCY_LAUNCH_W(T, MODE)                                                                                                  \
     hipLaunchKernelGGL((k_moments_weighted<T, MODE>), grid, dim3(256), 0, st, (const T *)Y, (const T *)X, (const T *)W, (const T *)M, \
@@ -618,8 +650,45 @@ extern "C" int vcy_fit_weighted(const void *Y, const void *X, int weight_mode, c
     }
 #undef VCY_LAUNCH_W
     VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_fit_weighted(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
+                                const double *scale_a, const double *scale_b, const double *down, const double *up,
+                                int fit_offset, int box_q, double lo_gamma, double up_gamma_default, const double *up_gamma,
+                                const double *q_fixed, float *gamma, float *q, float *R2, void *workspace, int64_t C, int64_t G,
+                                int64_t ld, int dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && X && gamma && workspace, "fit_weighted: null pointer");
+    hipStream_t st = as_stream(stream);
+    int rc = fit_weighted_partials(Y, X, weight_mode, W, M, M2, scale_a, scale_b, down, up, workspace, C, G, ld, dtype, st);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_fit_weighted_final, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const double *)workspace, fit_offset,
                        box_q, lo_gamma, up_gamma_default, up_gamma, q_fixed, gamma, q, R2, (int)C, (int)G);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_fit_weighted_moments(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
+                                        const double *scale_a, const double *scale_b, const double *down, const double *up, double *moments,
+                                        void *workspace, int64_t C, int64_t G, int64_t ld, int dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && X && moments && workspace, "fit_weighted_moments: null pointer");
+    hipStream_t st = as_stream(stream);
+    int rc = fit_weighted_partials(Y, X, weight_mode, W, M, M2, scale_a, scale_b, down, up, workspace, C, G, ld, dtype, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_fit_weighted_fold, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const double *)workspace, moments, (int)G);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_fit_weighted_from_moments(const double *moments, int64_t n_cells, int fit_offset, int box_q, double lo_gamma,
+                                             double up_gamma_default, const double *up_gamma, const double *q_fixed, float *gamma, float *q,
+                                             float *R2, int64_t G, vcy_stream stream)
+{
+    VCY_REQUIRE(moments && gamma && G > 0 && n_cells > 0, "fit_weighted_from_moments: bad arguments");
+    hipLaunchKernelGGL(k_fit_weighted_from_moments, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, as_stream(stream), moments, (double)n_cells,
+                       fit_offset, box_q, lo_gamma, up_gamma_default, up_gamma, q_fixed, gamma, q, R2, (int)G);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
 }

@@ -98,7 +98,7 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x)
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
 }
-__device__ __forceinline__ uint32_t perm_key(uint32_t seed_lo, uint32_t seed_hi, int g) { return mix32(seed_lo ^ mix32((uint32_t)g * 0x9e3779b9u + seed_hi)); }
+__device__ __forceinline__ uint32_t perm_key(uint32_t seed_lo, uint32_t seed_hi, int64_t g) { return mix32(seed_lo ^ mix32((uint32_t)g * 0x9e3779b9u + seed_hi)); }
 __device__ __forceinline__ uint32_t perm_cell(uint32_t c, uint32_t key, int hb, uint32_t C)
 {
     const uint32_t mask = (1u << hb) - 1u;
@@ -119,7 +119,7 @@ __device__ __forceinline__ uint32_t perm_sign(uint32_t c, uint32_t key) { return
 
 template <typename T, int CPT>
 __global__ __launch_bounds__(256) void k_permute_rows_nsign(const T *__restrict__ in, T *__restrict__ out, int C, int G, int64_t ld,
-                                                             uint32_t seed_lo, uint32_t seed_hi, int hb)
+                                                             uint32_t seed_lo, uint32_t seed_hi, int hb, int64_t gene0)
 {
     const int g = blockIdx.x * 256 + threadIdx.x;            // lanes = consecutive genes: coalesced stores, one sector per gathered value
     if (g >= ld) return;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void k_permute_rows_nsign(const T *__restrict_
         for (int c = c0; c < min(C, c0 + CPT); ++c) out[(int64_t)c * ld + g] = T(0);
         return;
     }
-    const uint32_t key = perm_key(seed_lo, seed_hi, g);
+    const uint32_t key = perm_key(seed_lo, seed_hi, gene0 + g);
     T v[CPT];
     uint32_t sg[CPT];
 #pragma unroll
@@ -147,10 +147,10 @@ __global__ __launch_bounds__(256) void k_permute_rows_nsign(const T *__restrict_
 // transposes and this kernel move 36 GB.  Lanes = consecutive cells of one gene.
 template <typename T, int CPT>
 __global__ __launch_bounds__(256) void k_permute_within_gene_rows(const T *__restrict__ in, T *__restrict__ out, int C, uint32_t seed_lo,
-                                                                   uint32_t seed_hi, int hb)
+                                                                   uint32_t seed_hi, int hb, int64_t gene0)
 {
     const int g = blockIdx.y;
-    const uint32_t key = perm_key(seed_lo, seed_hi, g);
+    const uint32_t key = perm_key(seed_lo, seed_hi, gene0 + g);
     const T *row = in + (int64_t)g * C;
     T *orow = out + (int64_t)g * C;
     const int c0 = blockIdx.x * 256 * CPT + threadIdx.x;
@@ -641,7 +641,7 @@ __device__ __forceinline__ void sparse_half(const SparseHalf &sp)
 // index is uniform over the block (scalar loads).  8 terms are folded in CT before they are added to the fp64 accumulator.
 template <typename CT, int EDIM, int JPT>
 __global__ __launch_bounds__(256) void k_gauss_transform(const CT *__restrict__ es, const CT *__restrict__ u, double *__restrict__ part, int n,
-                                                          int nparts, SparseHalf sp)
+                                                          int nparts, SparseHalf sp, int bx0 = 0)
 {
     __shared__ double s_tab[64];
     if ((int)blockIdx.y < sp.rows) { sparse_half(sp); return; }
@@ -650,7 +650,7 @@ __global__ __launch_bounds__(256) void k_gauss_transform(const CT *__restrict__ 
         __syncthreads();
     }
     const int by = (int)blockIdx.y - sp.rows;
-    const int j0 = blockIdx.x * 256 * JPT + threadIdx.x;
+    const int j0 = (bx0 + (int)blockIdx.x) * 256 * JPT + threadIdx.x;       // bx0: first target block (target-range steps)
     CT ej[JPT][EDIM];
 #pragma unroll
     for (int t = 0; t < JPT; ++t) {
@@ -724,14 +724,14 @@ __global__ void k_gauss_boxes(const CT *__restrict__ pts, int npts, CT *__restri
 template <typename CT, int EDIM, int JPT>
 __global__ __launch_bounds__(256) void k_gauss_transform_culled(const CT *__restrict__ es, const CT *__restrict__ u, double *__restrict__ part, int n,
                                                                  const CT *__restrict__ clo, const CT *__restrict__ chi, int nchunk, CT cut,
-                                                                 int nparts, SparseHalf sp)
+                                                                 int nparts, SparseHalf sp, int bx0 = 0)
 {
     __shared__ CT red[2][EDIM][4];
     __shared__ double s_tab[256];
     if ((int)blockIdx.y < sp.rows) { sparse_half(sp); return; }
     if (sizeof(CT) == 8) s_tab[threadIdx.x] = c_exp2_tab256[threadIdx.x];                       // 256 threads, published by the barrier below
     const int by = (int)blockIdx.y - sp.rows;
-    const int j0 = blockIdx.x * 256 * JPT + threadIdx.x;
+    const int j0 = (bx0 + (int)blockIdx.x) * 256 * JPT + threadIdx.x;       // bx0: first target block (target-range steps)
     CT ej[JPT][EDIM];
 #pragma unroll
     for (int t = 0; t < JPT; ++t) {
@@ -839,6 +839,36 @@ __global__ void k_gauss_reduce(const double *__restrict__ part, double *__restri
     u[jj] = (CT)(coef * vj / kw[j]);
 }
 
+// Target-range step (cell-sharded chains): the sparse half and the fold of the targets at positions t0 .. t0 + nt - 1 only (position =
+// cell, or the cell's place in `order` for the culled transform), with the arithmetic of sparse_half / k_gauss_reduce; the fold of
+// v / u for the next step is left out (the next step starts from the all-gathered state).
+__global__ void k_sparse_rows(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx, const double *__restrict__ scsc,
+                              const double *__restrict__ v, double *__restrict__ y, const int32_t *__restrict__ order, int64_t t0, int64_t nt)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nt) return;
+    const int64_t j = order ? (int64_t)order[t0 + i] : t0 + i;
+    double acc = 0.0;
+    for (int64_t p = colptr[j] + lane; p < colptr[j + 1]; p += 64) acc = fma(scsc[p], v[rowidx[p]], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) y[j] = acc;
+}
+
+__global__ void k_gauss_reduce_rows(const double *__restrict__ part, double *__restrict__ y, double *__restrict__ accum, int n, int nparts,
+                                    const int32_t *__restrict__ order, int64_t t0, int64_t nt)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nt) return;
+    const int64_t jj = t0 + i;
+    const int64_t j = order ? (int64_t)order[jj] : jj;
+    double s = 0.0;
+    for (int p = 0; p < nparts; ++p) s += part[(int64_t)p * n + jj];
+    s += y[j];
+    y[j] = s;
+    if (accum) accum[j] += s;
+}
+
 static inline int grid_for(int64_t total) { const int64_t b = (total + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 }  // namespace vcy
 
@@ -886,8 +916,8 @@ extern "C" size_t vcy_permute_rows_nsign_workspace_bytes(int64_t C, int64_t G, i
     return (size_t)C * (size_t)G * (dtype == VCY_F64 ? 8 : 4);
 }
 
-extern "C" int vcy_permute_rows_nsign(const void *in, void *out, void *workspace_a, void *workspace_b, int64_t C, int64_t G, int64_t ld,
-                                      uint64_t seed, int dtype, vcy_stream stream)
+static int permute_rows_nsign(const void *in, void *out, void *workspace_a, void *workspace_b, int64_t C, int64_t G, int64_t ld,
+                              int64_t gene0, uint64_t seed, int dtype, vcy_stream stream)
 {
     VCY_REQUIRE((workspace_a == nullptr) == (workspace_b == nullptr) && (!workspace_a || (workspace_a != workspace_b && workspace_a != in && workspace_b != in &&
                 workspace_a != out && workspace_b != out)), "permute_rows_nsign: the two scratch buffers go together and are distinct from in / out");
@@ -903,17 +933,30 @@ extern "C" int vcy_permute_rows_nsign(const void *in, void *out, void *workspace
         if (rc) return rc;
         constexpr int CPT = 4;
         const dim3 grid((unsigned)((C + 256 * CPT - 1) / (256 * CPT)), (unsigned)G);
-        if (dtype == VCY_F32) hipLaunchKernelGGL((k_permute_within_gene_rows<float, CPT>), grid, dim3(256), 0, st, (const float *)A, (float *)B, (int)C, lo, hi, hb);
-        else hipLaunchKernelGGL((k_permute_within_gene_rows<double, CPT>), grid, dim3(256), 0, st, (const double *)A, (double *)B, (int)C, lo, hi, hb);
+        if (dtype == VCY_F32) hipLaunchKernelGGL((k_permute_within_gene_rows<float, CPT>), grid, dim3(256), 0, st, (const float *)A, (float *)B, (int)C, lo, hi, hb, gene0);
+        else hipLaunchKernelGGL((k_permute_within_gene_rows<double, CPT>), grid, dim3(256), 0, st, (const double *)A, (double *)B, (int)C, lo, hi, hb, gene0);
         VCY_LAUNCH_CHECK();
         return vcy_transpose(B, out, G, C, C, ld, dtype, dtype, stream);
     }
     constexpr int CPT = 8;
     const dim3 grid((unsigned)((ld + 255) / 256), (unsigned)((C + CPT - 1) / CPT));
-    if (dtype == VCY_F32) hipLaunchKernelGGL((k_permute_rows_nsign<float, CPT>), grid, dim3(256), 0, st, (const float *)in, (float *)out, (int)C, (int)G, ld, lo, hi, hb);
-    else hipLaunchKernelGGL((k_permute_rows_nsign<double, CPT>), grid, dim3(256), 0, st, (const double *)in, (double *)out, (int)C, (int)G, ld, lo, hi, hb);
+    if (dtype == VCY_F32) hipLaunchKernelGGL((k_permute_rows_nsign<float, CPT>), grid, dim3(256), 0, st, (const float *)in, (float *)out, (int)C, (int)G, ld, lo, hi, hb, gene0);
+    else hipLaunchKernelGGL((k_permute_rows_nsign<double, CPT>), grid, dim3(256), 0, st, (const double *)in, (double *)out, (int)C, (int)G, ld, lo, hi, hb, gene0);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
+}
+
+extern "C" int vcy_permute_rows_nsign(const void *in, void *out, void *workspace_a, void *workspace_b, int64_t C, int64_t G, int64_t ld,
+                                      uint64_t seed, int dtype, vcy_stream stream)
+{
+    return permute_rows_nsign(in, out, workspace_a, workspace_b, C, G, ld, 0, seed, dtype, stream);
+}
+
+extern "C" int vcy_permute_rows_nsign_genes(const void *in, void *out, void *workspace_a, void *workspace_b, int64_t C, int64_t G, int64_t ld,
+                                            int64_t gene0, uint64_t seed, int dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(gene0 >= 0 && gene0 + G <= 65536ll * 256, "permute_rows_nsign_genes: bad gene offset");
+    return permute_rows_nsign(in, out, workspace_a, workspace_b, C, G, ld, gene0, seed, dtype, stream);
 }
 
 extern "C" int vcy_corr_fixup(void *vals, const int32_t *ixs, int64_t cell0, int64_t C_out, int64_t nrndm, int zero_self, int fix_nan,
@@ -1087,6 +1130,61 @@ static int diffuse_step_factored(const double *x, double *y, double *accum, cons
     hipLaunchKernelGGL(k_gauss_reduce<CT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double *)part, y, accum, (int)n, nparts, order, tot, kw, v, u, coef);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
+}
+
+template <typename CT>
+static int diffuse_step_factored_rows(const double *x, double *y, double *accum, const int64_t *colptr, const int32_t *rowidx, const double *scsc,
+                                      const double *tot, const double *kw, const CT *es, const int32_t *rank, const int32_t *order, const CT *boxes,
+                                      int edim, double sigma_W, double cut, void *workspace, int64_t n, int64_t t0, int64_t t1, hipStream_t st)
+{
+    if (t1 == t0) return VCY_OK;
+    double *v = (double *)workspace;
+    CT *u = (CT *)(v + n);
+    double *part = v + 2 * n;
+    const double coef = 0.2 / sqrt(2.0 * 3.14159265358979323846 * sigma_W * sigma_W);
+    const int64_t nt = t1 - t0;
+    hipLaunchKernelGGL(k_markov_scale_x<CT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, tot, kw, v, u, (int)n, coef, boxes ? rank : nullptr);
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sparse_rows, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, colptr, rowidx, scsc, (const double *)v, y,
+                       boxes ? order : nullptr, t0, nt);
+    VCY_LAUNCH_CHECK();
+    SparseHalf sp{colptr, rowidx, scsc, (const double *)v, y, (int)n, 0};                  // rows = 0: the sparse half ran above
+    int nparts;
+    if (boxes) {                                           // the full step's target blocks (256 positions) and source chunks
+        const int64_t nc = gt_chunks(n);
+        nparts = nc < 64 ? (int)nc : 64;
+        const CT *clo = boxes, *chi = clo + nc * edim;
+        const int bx0 = (int)(t0 / 256), bx1 = (int)((t1 + 255) / 256);
+        dim3 gridc((unsigned)(bx1 - bx0), (unsigned)nparts);
+#define VCY_GTC(ED) hipLaunchKernelGGL((k_gauss_transform_culled<CT, ED, 1>), gridc, dim3(256), 0, st, es, (const CT *)u, part, (int)n, clo, chi, (int)nc, (CT)cut, nparts, sp, bx0)
+        switch (edim) { case 1: VCY_GTC(1); break; case 2: VCY_GTC(2); break; case 3: VCY_GTC(3); break; default: VCY_GTC(4); break; }
+#undef VCY_GTC
+    } else {                                               // the full step's target blocks (512 cells) and source parts
+        nparts = gauss_parts(n);
+        const int bx0 = (int)(t0 / 512), bx1 = (int)((t1 + 511) / 512);
+        dim3 grid((unsigned)(bx1 - bx0), (unsigned)nparts);
+#define VCY_GT(ED) hipLaunchKernelGGL((k_gauss_transform<CT, ED, 2>), grid, dim3(256), 0, st, es, (const CT *)u, part, (int)n, nparts, sp, bx0)
+        switch (edim) { case 1: VCY_GT(1); break; case 2: VCY_GT(2); break; case 3: VCY_GT(3); break; default: VCY_GT(4); break; }
+#undef VCY_GT
+    }
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_gauss_reduce_rows, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, (const double *)part, y, accum, (int)n, nparts,
+                       boxes ? order : nullptr, t0, nt);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_diffuse_step_factored_rows(const double *x, double *y, double *accum, const int64_t *colptr, const int32_t *rowidx,
+                                              const double *scsc, const double *tot, const double *kw, const void *es, const int32_t *rank,
+                                              const int32_t *order, const void *boxes, int edim, double sigma_W, double cut, void *workspace,
+                                              int64_t n, int64_t t0, int64_t t1, int compute_dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(x && y && colptr && rowidx && scsc && tot && kw && es && workspace && x != y, "diffuse_step_factored_rows: bad arguments");
+    VCY_REQUIRE(n > 0 && n < (1ll << 31) && edim > 0 && edim <= 4 && sigma_W > 0 && 0 <= t0 && t0 <= t1 && t1 <= n, "diffuse_step_factored_rows: bad arguments");
+    VCY_REQUIRE(!boxes || (rank && order && cut > 0), "diffuse_step_factored_rows: the culled step needs rank, order and cut");
+    if (compute_dtype == VCY_F32) return diffuse_step_factored_rows<float>(x, y, accum, colptr, rowidx, scsc, tot, kw, (const float *)es, rank, order, (const float *)boxes, edim, sigma_W, cut, workspace, n, t0, t1, as_stream(stream));
+    if (compute_dtype == VCY_F64) return diffuse_step_factored_rows<double>(x, y, accum, colptr, rowidx, scsc, tot, kw, (const double *)es, rank, order, (const double *)boxes, edim, sigma_W, cut, workspace, n, t0, t1, as_stream(stream));
+    return fail(VCY_ERR_INVALID, "%s: bad dtype", "diffuse_step_factored_rows");
 }
 
 extern "C" size_t vcy_markov_cull_boxes_bytes(int64_t n, int edim, int compute_dtype)

@@ -320,6 +320,60 @@ class HaloPlan:
         return out
 
 
+class GeneSlices:
+    """Exchange of a cells-sharded matrix to GENE slices and back (the per-gene passes that need every cell: the percentiles of
+    fit_gammas, the shuffle of the randomised control).
+
+    Rank r holds cells [c0_r, c1_r) (shard_bounds) of the run's cell order, and its gene slice is genes [g0_r, g1_r) =
+    shard_bounds(G) of EVERY cell, rows in the user's cell order: `user_row` (int64, C) is the user's number of each cell of the
+    run's order.  Each direction is one all_to_all_uneven of gene-major blocks, packed and unpacked by one transposing kernel each
+    (ops.gene_slices_pack / _unpack; the relabelling is applied in the same pass).  A pass moves every element once: C x G x the
+    element size over all ranks, (1 - 1/world) of it between ranks."""
+
+    def __init__(self, n_cells: int, n_genes: int, user_row: torch.Tensor, group=None):
+        self.rank, self.ws = world()
+        self.C, self.G, self.group = int(n_cells), int(n_genes), group
+        self.user_row = user_row.to(torch.int64).contiguous()
+        assert self.user_row.numel() == self.C
+        dev = self.user_row.device
+        self.cells = all_shard_bounds(self.C, self.ws)
+        self.genes = all_shard_bounds(self.G, self.ws)
+        self.c0, self.c1 = self.cells[self.rank]
+        self.g0, self.g1 = self.genes[self.rank]
+        self.nloc, self.gs = self.c1 - self.c0, self.g1 - self.g0
+        self._seg_cells = torch.tensor([0] + [b for _, b in self.cells], dtype=torch.int64, device=dev)
+        self._seg_one = torch.tensor([0, self.nloc], dtype=torch.int64, device=dev)
+        self.bytes_moved = 0                     # bytes this rank sent to other ranks, all passes
+
+    def _a2a(self, send: torch.Tensor, send_splits, recv_splits) -> torch.Tensor:
+        if not active():
+            return send
+        self.bytes_moved += (int(sum(send_splits)) - int(send_splits[self.rank])) * send.element_size()
+        return all_to_all_uneven(send, send_splits, recv_splits, group=self.group)
+
+    def to_slices(self, local):
+        """local: the rank's (c1 - c0, >= G) rows (ops.CellMatrix) -> its gene slice, an ops.CellMatrix (C, gs) in the user's order."""
+        from . import ops
+        assert local.C == self.nloc and local.G == self.G
+        buf = ops.gene_slices_pack(local, self._seg_one)                        # (G, nloc) gene-major: destination r = genes g0_r..g1_r
+        recv = self._a2a(buf, [(b - a) * self.nloc for a, b in self.genes], [self.gs * (b - a) for a, b in self.cells])
+        out = ops.CellMatrix.empty(self.C, self.gs, local.dtype)
+        return ops.gene_slices_unpack(recv, self._seg_cells, out, row_map=self.user_row)
+
+    def from_slices(self, sl, out=None):
+        """The inverse: a gene slice (C, gs) in the user's order -> the rank's rows (c1 - c0, G) (ops.CellMatrix, or into `out`)."""
+        from . import ops
+        assert sl.C == self.C and sl.G == self.gs
+        buf = ops.gene_slices_pack(sl, self._seg_cells, row_map=self.user_row)   # per destination s: (gs, n_s) gene-major
+        recv = self._a2a(buf, [self.gs * (b - a) for a, b in self.cells], [(b - a) * self.nloc for a, b in self.genes])
+        out = ops.CellMatrix.empty(self.nloc, self.G, sl.dtype) if out is None else out
+        return ops.gene_slices_unpack(recv, self._seg_one, out)
+
+    def gather_genes(self, v: torch.Tensor) -> torch.Tensor:
+        """Per-gene results of the slice, (gs, ...) -> (G, ...) on every rank."""
+        return all_gather_rows(v.contiguous(), self.G, group=self.group)
+
+
 def overlap_schedules(base: torch.Tensor, interior: torch.Tensor, cells_per_round: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Two stage-D schedules for the halo overlap: (cells that run WHILE the halo rows move, cells that run after).
 

@@ -1374,6 +1374,62 @@ def fit_weighted(Y: CellMatrix, X: CellMatrix, weight_mode: int, W: Optional[Cel
     return gamma, q, R2
 
 
+def fit_weighted_moments(Y: CellMatrix, X: CellMatrix, weight_mode: int, W: Optional[CellMatrix] = None, M: Optional[CellMatrix] = None,
+                         M2: Optional[CellMatrix] = None, scale_a=None, scale_b=None, down=None, up=None) -> torch.Tensor:
+    """First half of fit_weighted for a block of cells (vcy_fit_weighted_moments): (10, G) fp64 moments [Sx Sy Sxx Sxy Syy | Sw Swx
+    Swy Swxx Swxy] that add up over blocks (an all-reduce in cell-sharded runs) before fit_weighted_from_moments solves them."""
+    dev = Y.t.device
+    mom = torch.empty((10, Y.G), dtype=torch.float64, device=dev)
+    ws = _fit_workspace(Y.G, dev)
+    f64 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float64).contiguous()
+    scale_a, scale_b, down, up = map(f64, (scale_a, scale_b, down, up))
+    _lib.check(_lib.lib().vcy_fit_weighted_moments(Y.t.data_ptr(), X.t.data_ptr(), weight_mode, None if W is None else W.t.data_ptr(),
+                                                   None if M is None else M.t.data_ptr(), None if M2 is None else M2.t.data_ptr(),
+                                                   _p(scale_a), _p(scale_b), _p(down), _p(up), mom.data_ptr(), ws.data_ptr(), Y.C, Y.G, Y.ld,
+                                                   Y.code, _stream()), "fit_weighted_moments")
+    return mom
+
+
+def fit_weighted_from_moments(mom: torch.Tensor, n_cells: int, fit_offset: bool = True, box_q: bool = True, lo_gamma: float = 1e-8,
+                              up_gamma_default: float = 20.0, up_gamma=None, q_fixed=None, want_R2: bool = True
+                              ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Second half of fit_weighted (vcy_fit_weighted_from_moments): (gamma, q, R2) float32 from moments summed over n_cells cells."""
+    dev = mom.device
+    G = int(mom.shape[1])
+    assert mom.dtype == torch.float64 and tuple(mom.shape) == (10, G) and mom.is_contiguous()
+    gamma = torch.empty(G, dtype=torch.float32, device=dev)
+    q = torch.empty(G, dtype=torch.float32, device=dev)
+    R2 = torch.empty(G, dtype=torch.float32, device=dev) if want_R2 else None
+    f64 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float64).contiguous()
+    up_gamma, q_fixed = f64(up_gamma), f64(q_fixed)
+    _lib.check(_lib.lib().vcy_fit_weighted_from_moments(mom.data_ptr(), int(n_cells), int(fit_offset), int(box_q), float(lo_gamma),
+                                                        float(up_gamma_default), _p(up_gamma), _p(q_fixed), gamma.data_ptr(), q.data_ptr(),
+                                                        _p(R2), G, _stream()), "fit_weighted_from_moments")
+    return gamma, q, R2
+
+
+def gene_slices_pack(src: CellMatrix, seg: torch.Tensor, row_map: Optional[torch.Tensor] = None, N: Optional[int] = None) -> torch.Tensor:
+    """Cells-major `src` -> the gene-major wire layout of the gene-slice exchange (vcy_gene_slices_pack): the N buffer cells in the
+    segments `seg` (int64, seg[0] = 0, seg[-1] = N), cell c read from row row_map[c] of src (identity when None)."""
+    N = (src.C if row_map is None else int(row_map.numel())) if N is None else int(N)
+    buf = torch.empty(N * src.G, dtype=src.dtype, device=src.t.device)
+    if N and src.G:
+        _lib.check(_lib.lib().vcy_gene_slices_pack(src.t.data_ptr(), _p(row_map), seg.data_ptr(), int(seg.numel()) - 1, buf.data_ptr(), N, src.G,
+                                                   src.ld, src.code, _stream()), "gene_slices_pack")
+    return buf
+
+
+def gene_slices_unpack(buf: torch.Tensor, seg: torch.Tensor, dst: CellMatrix, row_map: Optional[torch.Tensor] = None,
+                       N: Optional[int] = None) -> CellMatrix:
+    """The inverse of gene_slices_pack into the cells-major `dst` (vcy_gene_slices_unpack)."""
+    N = (dst.C if row_map is None else int(row_map.numel())) if N is None else int(N)
+    assert buf.numel() == N * dst.G and buf.dtype == dst.dtype
+    if N and dst.G:
+        _lib.check(_lib.lib().vcy_gene_slices_unpack(buf.data_ptr(), _p(row_map), seg.data_ptr(), int(seg.numel()) - 1, dst.t.data_ptr(), N, dst.G,
+                                                     dst.ld, dst.code, _stream()), "gene_slices_unpack")
+    return dst
+
+
 # --------------------------------------------------------------------------- stage C
 def velocity_chain(Sx_sz: CellMatrix, Ux_sz: CellMatrix, gamma: torch.Tensor, q: Optional[torch.Tensor], *, want=("dmat",),
                    eps_thr: Optional[torch.Tensor] = None, dt_shift: float = 1.0, dt_extrap: float = 1.0, used_dt: float = 1.0,
@@ -1441,13 +1497,14 @@ def delta_transform(hi_dim: CellMatrix, delta_S: CellMatrix, used_dt: float, mod
 
 
 def permute_rows_nsign(delta_S: CellMatrix, seed: int, gene_major: Optional[bool] = None,
-                       scratch: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> CellMatrix:
+                       scratch: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, gene0: int = 0) -> CellMatrix:
     """The randomised control's delta_S (analysis.py:2407-2420): per gene, the values shuffled across the cells by an independent
     pseudo-random permutation and multiplied by independent random signs (vcy_permute_rows_nsign; a function of (seed, gene, cell),
     statistical parity with the reference's numba stream).  gene_major: shuffle on a gene-major copy (two matrix-sized scratch
     buffers, three streaming passes) instead of one gather with a sector per value; None = when the matrix is large and the scratch
     is given or fits in the free memory.  scratch: two device buffers of at least the matrix's size to use for it (their contents
-    are destroyed) - e.g. the buffers the caller is about to fill anyway.  Same result either way."""
+    are destroyed) - e.g. the buffers the caller is about to fill anyway.  Same result either way.  gene0: the matrix is a gene
+    slice whose column j is gene gene0 + j of the whole matrix (vcy_permute_rows_nsign_genes, the sharded control)."""
     L = _lib.lib()
     out = CellMatrix(torch.empty_like(delta_S.t), delta_S.G)
     need = int(L.vcy_permute_rows_nsign_workspace_bytes(delta_S.C, delta_S.G, delta_S.code))
@@ -1459,6 +1516,10 @@ def permute_rows_nsign(delta_S: CellMatrix, seed: int, gene_major: Optional[bool
     a = b = None
     if gene_major:
         a, b = scratch if scratch is not None else (torch.empty(need, dtype=torch.uint8, device=delta_S.t.device) for _ in range(2))
+    if gene0:
+        _lib.check(L.vcy_permute_rows_nsign_genes(delta_S.t.data_ptr(), out.t.data_ptr(), _p(a), _p(b), delta_S.C, delta_S.G, delta_S.ld,
+                                                  int(gene0), int(seed) & (2**64 - 1), delta_S.code, _stream()), "permute_rows_nsign_genes")
+        return out
     _lib.check(L.vcy_permute_rows_nsign(delta_S.t.data_ptr(), out.t.data_ptr(), _p(a), _p(b), delta_S.C, delta_S.G, delta_S.ld,
                                         int(seed) & (2**64 - 1), delta_S.code, _stream()), "permute_rows_nsign")
     return out
@@ -1607,6 +1668,26 @@ def diffuse(x0, tr, n_steps: int, accumulate: bool) -> Tuple[torch.Tensor, Optio
     return x, acc
 
 
+def diffuse_step_rows(tr: "MarkovFactors", x: torch.Tensor, y: torch.Tensor, t0: int, t1: int, accum: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One step x -> y of the factored chain for the targets at positions [t0, t1) only (vcy_diffuse_step_factored_rows): positions
+    are cells, or places in `tr.target_order()` when the chain steps with the culled transform.  Only those entries of y (and accum)
+    are written, with the full step's values."""
+    L = _lib.lib()
+    n = tr.n
+    assert x.dtype == y.dtype == torch.float64 and x.numel() == y.numel() == n and x.is_contiguous() and y.is_contiguous()
+    ws = workspace if workspace is not None else torch.empty(int(L.vcy_markov_factored_workspace_bytes(n)), dtype=torch.uint8, device=x.device)
+    if tr.cull is not None:
+        es, rank, boxes, cut, order = tr.cull
+    else:
+        es, rank, boxes, cut, order = tr.es, None, None, 0.0, None
+    _lib.check(L.vcy_diffuse_step_factored_rows(x.data_ptr(), y.data_ptr(), _p(accum), tr.colptr.data_ptr(), tr.rowidx.data_ptr(), tr.scsc.data_ptr(),
+                                                tr.tot.data_ptr(), tr.kw.data_ptr(), es.data_ptr(), _p(rank), _p(order), _p(boxes), tr.edim,
+                                                tr.sigma_W, float(cut), ws.data_ptr(), n, int(t0), int(t1), _DT[tr.compute_dtype], _stream()),
+               "diffuse_step_factored_rows")
+    return y
+
+
 def gamma_weights(S: CellMatrix, U: Optional[CellMatrix], mode: int, pa, pb, pc=None, pd=None, sa=None, sb=None, power: float = 15.0) -> CellMatrix:
     """Dense W for the non-default fit_gammas weight modes (see vcy_gamma_weights)."""
     dev = S.t.device
@@ -1649,6 +1730,12 @@ class MarkovFactors:
         _lib.check(_lib.lib().vcy_markov_cull_boxes(es_sorted.data_ptr(), boxes.data_ptr(), self.n, self.edim, code, _stream()), "markov_cull_boxes")
         self.cull = (es_sorted, rank, boxes, float(cut), order.to(torch.int32).contiguous())
         return self
+
+    def target_order(self) -> torch.Tensor:
+        """The cell at each target position of diffuse_step_rows (int64): the sorted order of the culled transform, else the identity."""
+        if self.cull is not None:
+            return self.cull[4].long()
+        return torch.arange(self.n, device=self.es.device)
 
     def dense(self, dtype=torch.float64) -> torch.Tensor:
         ip, ix, pv = self._csr
