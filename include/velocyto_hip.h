@@ -557,6 +557,26 @@ int vcy_svr_rbf_fit(const double *x, const double *t, double *coef, double *inte
 int vcy_svr_rbf_predict(const double *x, const double *coef, const double *intercept, const double *xq, double *out, int64_t n,
                         int64_t m, double gamma, vcy_stream stream);
 
+/* ---------------------------------------------------------------- upstream caller: t-SNE of the PCs
+ * perform_TSNE (analysis.py:1441-1450: sklearn.manifold.TSNE(n_components, perplexity, angle=theta, init, max_iter), Barnes-Hut).
+ * vcy_tsne_perplexity replaces sklearn.manifold._utils._binary_search_perplexity: sqd (N, k) f32 squared distances of every row's k
+ * neighbours, in the order the sums run (scikit-learn: by neighbour index) -> P (N, k) f64 conditional probabilities of the given
+ * perplexity (rounded to f32, as there); n_steps (N) int32 or NULL: bisection steps the row took, 0 when all 100 ran without
+ * meeting the tolerance.
+ * vcy_tsne_gradient replaces sklearn.manifold._t_sne._kl_divergence_bh with the repulsion summed over ALL pairs (the angle -> 0
+ * limit of the Barnes-Hut tree): Y (N, n_components) f32 positions, P as CSR (indptr int64 (N + 1), indices int32, pval f32),
+ * grad (N, n_components) f32, stats (>= 3) f64 = [Z, KL (when compute_error), |grad|^2]; n_components 1..3, dof = max(n_components - 1, 1).
+ * vcy_tsne_step is one iteration of sklearn.manifold._t_sne._gradient_descent on the same objective: Y_out = Y + update, with
+ * update (N, n_components) f64 and gains f32 updated in place (Y_out must not alias Y); stats as above with |grad|^2 taken after the
+ * gains, KL and |grad|^2 written only when compute_error.  Deterministic (no atomics).  workspace: vcy_tsne_workspace_bytes(N, n_components). */
+size_t vcy_tsne_workspace_bytes(int64_t N, int n_components);
+int vcy_tsne_perplexity(const float *sqd, double *P, int32_t *n_steps, int64_t N, int64_t k, double perplexity, vcy_stream stream);
+int vcy_tsne_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, float *grad, double *stats,
+                      void *workspace, int64_t N, int n_components, int compute_error, vcy_stream stream);
+int vcy_tsne_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval, double *update,
+                  float *gains, double *stats, void *workspace, int64_t N, int n_components, double momentum, double learning_rate,
+                  double min_gain, int compute_error, vcy_stream stream);
+
 /* ---------------------------------------------------------------- host helper: neighbour sampling of estimate_transition_prob
  * analysis.py:1561-1564 draws, per cell, np.random.choice(n, size, replace=False, p=p) from numpy's legacy global RNG.  This is
  * RandomState.choice(replace=False, p) restated over a pool of uniforms the caller drew from the same RandomState in one call

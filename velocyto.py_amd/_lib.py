@@ -85,6 +85,10 @@ SIGNATURES = {
     "vcy_svr_workspace_bytes": (c_i64, [c_i64]),
     "vcy_svr_rbf_fit": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_i64, c_vp]),
     "vcy_svr_rbf_predict": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp]),
+    "vcy_tsne_workspace_bytes": (c_sz, [c_i64, c_int]),
+    "vcy_tsne_perplexity": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp]),
+    "vcy_tsne_gradient": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "vcy_tsne_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp]),
     "vcy_quantile_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_gene_quantiles": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_dbl), c_int, c_vp, c_vp, c_i64,
                                    c_i64, c_i64, c_int, c_vp]),

@@ -1321,6 +1321,64 @@ def svr_predict(x, coef, intercept, xq, gamma: float) -> torch.Tensor:
     return out
 
 
+def tsne_perplexity(sqd, perplexity: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scikit-learn's _binary_search_perplexity on the device: sqd (N, k) squared distances to every row's neighbours, rounded to
+    f32, in the order the sums run (scikit-learn: by neighbour index) -> (conditional P (N, k) f64, bisection steps (N) int32,
+    0 where all 100 steps ran without meeting the tolerance)."""
+    dev = require_gpu()
+    d = torch.as_tensor(sqd, device=dev).to(torch.float32).contiguous()
+    if d.dim() != 2 or d.shape[0] < 1 or d.shape[1] < 1:
+        raise ValueError(f"tsne_perplexity: sqd must be a non-empty (N, k) array, got shape {tuple(d.shape)}")
+    N, k = d.shape
+    P = torch.empty((N, k), dtype=torch.float64, device=dev)
+    steps = torch.empty(N, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().vcy_tsne_perplexity(d.data_ptr(), P.data_ptr(), steps.data_ptr(), N, k, float(perplexity), _stream()), "tsne_perplexity")
+    return P, steps
+
+
+def _tsne_shapes(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor) -> Tuple[int, int]:
+    """What the t-SNE kernels index by: positions (N, d) f32 and P as CSR (indptr int64 (N + 1), indices int32, values f32)."""
+    if Y.dim() != 2 or Y.dtype != torch.float32 or not Y.is_contiguous():
+        raise ValueError("t-SNE positions must be a contiguous (N, n_components) float32 device tensor")
+    N, d = Y.shape
+    if (indptr.dtype != torch.int64 or indptr.numel() != N + 1 or indices.dtype != torch.int32 or pval.dtype != torch.float32
+            or indices.numel() != pval.numel() or not (indptr.is_contiguous() and indices.is_contiguous() and pval.is_contiguous())):
+        raise ValueError("t-SNE P must be CSR: indptr int64 (N + 1), indices int32 and values float32 of the same length")
+    return N, d
+
+
+def tsne_workspace(N: int, n_components: int) -> torch.Tensor:
+    return torch.empty(int(_lib.lib().vcy_tsne_workspace_bytes(N, n_components)), dtype=torch.uint8, device=require_gpu())
+
+
+def tsne_gradient(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, compute_error: bool = True,
+                  ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The gradient of scikit-learn's _kl_divergence_bh with the repulsion summed over all pairs (its angle -> 0 limit):
+    (grad (N, d) f32, stats (4) f64 = [Z, KL (0 unless compute_error), |grad|^2, 0])."""
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    grad = torch.empty_like(Y)
+    stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
+    ws = tsne_workspace(N, d) if ws is None else ws
+    _lib.check(_lib.lib().vcy_tsne_gradient(Y.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), grad.data_ptr(),
+                                            stats.data_ptr(), ws.data_ptr(), N, d, int(compute_error), _stream()), "tsne_gradient")
+    return grad, stats
+
+
+def tsne_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, update: torch.Tensor,
+              gains: torch.Tensor, stats: torch.Tensor, ws: torch.Tensor, momentum: float, learning_rate: float, min_gain: float = 0.01,
+              compute_error: bool = False) -> None:
+    """One iteration of scikit-learn's _gradient_descent on that objective: Y_out = Y + update, update (f64) and gains (f32) in
+    place; stats = [Z, KL, |grad * gains|^2, .] (KL and the norm only with compute_error)."""
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    if not (Y_out.shape == Y.shape and Y_out.dtype == torch.float32 and update.shape == Y.shape and update.dtype == torch.float64
+            and gains.shape == Y.shape and gains.dtype == torch.float32 and stats.numel() >= 4 and stats.dtype == torch.float64
+            and ws.numel() >= int(_lib.lib().vcy_tsne_workspace_bytes(N, d))):
+        raise ValueError("tsne_step: Y_out (N, d) f32, update (N, d) f64, gains (N, d) f32, stats (4) f64 and a workspace of tsne_workspace(N, d)")
+    _lib.check(_lib.lib().vcy_tsne_step(Y.data_ptr(), Y_out.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), update.data_ptr(),
+                                        gains.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, float(momentum), float(learning_rate),
+                                        float(min_gain), int(compute_error), _stream()), "tsne_step")
+
+
 def select_cells(M, keep) -> "CellMatrix":
     """Cell (row) subset of a cells-major matrix (CellMatrix or CountMatrix)."""
     idx = torch.nonzero(torch.as_tensor(keep, device=M.t.device), as_tuple=False).ravel()

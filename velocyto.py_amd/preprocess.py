@@ -12,7 +12,9 @@ What runs where:
     vcy_gram_tn, vcy_gemm_nt - the matrix is read as stored, centring is algebra), the small eigensolvers / QR are library calls;
   * the SVR noise models of score_cv_vs_mean (one point per gene) and adjust_totS_totU (one point per cell), which the
     reference delegates to scikit-learn / libsvm, are fitted by the same SMO iteration on the device (``DeviceSVR`` ->
-    ``vcy_svr_rbf_fit``: 0.5-0.7 s at 50 000 points against about a minute for libsvm); t-SNE stays with scikit-learn.
+    ``vcy_svr_rbf_fit``: 0.5-0.7 s at 50 000 points against about a minute for libsvm);
+  * t-SNE: scikit-learn by default, as the reference; ``perform_TSNE(backend="hip")`` runs ``tsne.DeviceTSNE`` (csrc/tsne.hip:
+    the perplexity search, the exact all-pairs gradient and the optimiser on the device).
 Plotting is out of scope (``plot=True`` is accepted and ignored).
 """
 from __future__ import annotations
@@ -495,9 +497,20 @@ class PreprocessMixin:
         self.pcsx = self.pcax.fit_transform(self.dev("Sx_norm"))
 
     def perform_TSNE(self, n_dims: int = 2, perplexity: float = 30, initial_pos: np.ndarray = None, theta: float = 0.5, n_pca_dim: int = None,
-                     max_iter: int = 1000) -> None:
-        """analysis.py:1441-1450: Barnes-Hut t-SNE of the leading PCs (scikit-learn, as the reference; its ``n_iter`` keyword is
-        ``max_iter`` since scikit-learn 1.5)."""
+                     max_iter: int = 1000, backend: str = "sklearn") -> None:
+        """analysis.py:1441-1450: Barnes-Hut t-SNE of the leading PCs -> ``ts`` (cells, n_dims).
+
+        backend="sklearn" (the default): scikit-learn, as the reference (its ``n_iter`` keyword is ``max_iter`` since scikit-learn 1.5).
+        backend="hip": ``tsne.DeviceTSNE`` with the same arguments on the device - the exact all-pairs gradient (``theta`` is accepted
+        and ignored: the result is the theta -> 0 limit of scikit-learn's), float32 ``ts``.  The keyword is temporary: once the device
+        path's measurements are recorded the default flips to it and the option goes away."""
+        if backend == "hip":
+            from .tsne import DeviceTSNE
+            self.ts = DeviceTSNE(n_components=n_dims, perplexity=perplexity, angle=theta, init="random" if initial_pos is None else initial_pos,
+                                 max_iter=max_iter).fit_transform(self.pcs[:, :n_pca_dim])
+            return
+        if backend != "sklearn":
+            raise ValueError(f"backend must be 'sklearn' or 'hip', got {backend!r}")
         import inspect
         from sklearn.manifold import TSNE
         kw = "max_iter" if "max_iter" in inspect.signature(TSNE.__init__).parameters else "n_iter"
