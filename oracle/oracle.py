@@ -1107,3 +1107,156 @@ def svr_rbf_predict(x, coef, intercept, xq, gamma):
     """SVR.predict: sum_k coef_k exp(-gamma (xq - x_k)^2) + intercept."""
     x, xq = np.asarray(x, dtype=np.float64).ravel(), np.asarray(xq, dtype=np.float64).ravel()
     return (coef[None, :] * np.exp(-gamma * (xq[:, None] - x[None, :]) ** 2)).sum(1) + intercept
+
+
+# --------------------------------------------------------------------------- t-SNE (csrc/tsne.hip, velocyto.py_amd/tsne.py)
+# Plain f64 restatements of what the device t-SNE computes.  Nothing here imports scikit-learn; tests/test_tsne_oracle.py pins
+# these functions on scikit-learn's private functions where it is installed, and on closed forms everywhere.
+_TSNE_TOL = float(np.float32(1e-5))            # PERPLEXITY_TOLERANCE, an f32 constant
+_TSNE_EPS = float(np.float32(1e-8))            # EPSILON_DBL, an f32 constant
+_TSNE_ZMIN = float(np.float32(np.finfo(np.float64).eps))   # the floor of sum_Q: FLOAT64_EPS held in a float
+_TSNE_TINY = float(np.finfo(np.float32).tiny)  # FLT_MIN
+
+
+def tsne_binary_search_perplexity(sqd, perplexity, n_steps=100):
+    """The bisection documented at the top of csrc/tsne.hip (scikit-learn's _binary_search_perplexity): for every row of the
+    f32 squared distances ``sqd`` (N, k) find beta with H(P) = log(perplexity), P_j = exp(-d_j beta) / sum.  f64 arithmetic,
+    every sum sequential in the row's order, the perplexity rounded to f32 before the log, tolerance 1e-5f, at most 100 steps,
+    sum_P == 0 replaced by 1e-8f.
+    Returns (P (N, k) f64, steps (N) int32 - the number of steps evaluated when the row met the tolerance, 0 when it used all of
+    them without meeting it, margin (N) f64 - the smallest | |diff| - tol | over the steps the row evaluated: how close the row
+    came to stopping a step earlier or later)."""
+    d = np.asarray(sqd, dtype=np.float32).astype(np.float64)
+    N, k = d.shape
+    H = np.log(np.float64(np.float32(perplexity)))
+    beta = np.ones(N)
+    lo, hi = np.full(N, -np.inf), np.full(N, np.inf)
+    P = np.zeros((N, k))
+    steps = np.zeros(N, dtype=np.int32)
+    margin = np.full(N, np.inf)
+    act = np.arange(N)
+    with np.errstate(under="ignore", over="ignore"):
+        for l in range(n_steps):
+            if act.size == 0:
+                break
+            da, b = d[act], beta[act]
+            p = np.exp(-da * b[:, None])
+            sum_P = np.zeros(act.size)
+            for j in range(k):
+                sum_P = sum_P + p[:, j]
+            sum_P[sum_P == 0.0] = _TSNE_EPS
+            p = p / sum_P[:, None]
+            sum_dP = np.zeros(act.size)
+            for j in range(k):
+                sum_dP = sum_dP + da[:, j] * p[:, j]
+            diff = (np.log(sum_P) + b * sum_dP) - H
+            P[act] = p
+            margin[act] = np.minimum(margin[act], np.abs(np.abs(diff) - _TSNE_TOL))
+            done = np.abs(diff) <= _TSNE_TOL
+            steps[act[done]] = l + 1
+            up = diff > 0.0
+            a_lo, a_hi = lo[act], hi[act]
+            a_lo = np.where(up, b, a_lo)
+            a_hi = np.where(up, a_hi, b)
+            nb = np.where(up, np.where(np.isinf(a_hi), b * 2.0, (b + a_hi) / 2.0), np.where(np.isinf(a_lo), b / 2.0, (b + a_lo) / 2.0))
+            go = ~done
+            lo[act[go]], hi[act[go]], beta[act[go]] = a_lo[go], a_hi[go], nb[go]
+            act = act[go]
+    return P, steps, margin
+
+
+def tsne_joint_p(idx, cond):
+    """_joint_probabilities_nn after the bisection: the dense f64 C + C^T for C[i, idx[i, j]] = cond[i, j], divided by
+    max(sum, DBL_EPSILON).  Returns CSR (indptr int64, indices int32, values f64) with sorted columns; entries that sum to
+    exactly 0 are dropped, as scipy's sparse addition drops them."""
+    import math
+    idx = np.asarray(idx, dtype=np.int64)
+    cond = np.asarray(cond, dtype=np.float64)
+    N = idx.shape[0]
+    C = np.zeros((N, N))
+    C[np.repeat(np.arange(N), idx.shape[1]), idx.ravel()] = cond.ravel()
+    P = C + C.T
+    r, c = np.nonzero(P)                               # row-major: sorted columns inside every row
+    v = P[r, c]
+    v = v / max(math.fsum(v), float(np.finfo(np.float64).eps))
+    indptr = np.zeros(N + 1, dtype=np.int64)
+    indptr[1:] = np.cumsum(np.bincount(r, minlength=N))
+    return indptr, c.astype(np.int32), v
+
+
+def _tsne_kl_terms(p, q, Z):
+    with np.errstate(under="ignore"):
+        qz = (q / Z).astype(np.float32).astype(np.float64)
+    return float(np.sum(p * np.log(np.maximum(p, _TSNE_TINY) / np.maximum(qz, _TSNE_TINY))))
+
+
+def tsne_kl(Y, indptr, indices, pval, Z):
+    """The KL of tsne_objective at a given normaliser Z: sum_e p_e log(max(p_e, FLT_MIN) / max(float32(w_ie / Z), FLT_MIN)).
+    KL depends on Z through -sum(p) log Z, so an error of Z enters it in full; this is KL as a function of the Z a kernel used."""
+    Y = np.asarray(Y, dtype=np.float32).astype(np.float64)
+    indptr = np.asarray(indptr, dtype=np.int64)
+    indices = np.asarray(indices, dtype=np.int64)[: indptr[-1]]
+    p = np.asarray(pval, dtype=np.float32).astype(np.float64)[: indptr[-1]]
+    dof = float(max(Y.shape[1] - 1, 1))
+    dd = Y[np.repeat(np.arange(Y.shape[0]), np.diff(indptr))] - Y[indices]
+    return _tsne_kl_terms(p, (dof / (dof + (dd * dd).sum(-1))) ** ((dof + 1.0) / 2.0), float(Z))
+
+
+def tsne_objective(Y, indptr, indices, pval, n_components=None, chunk=256):
+    """What k_tsne_repulsion + k_tsne_step compute, for positions Y (N, D) and CSR P values as the kernels read them (f32
+    values) in f64 arithmetic at dof = max(D - 1, 1): w_ij = (dof / (dof + d_ij^2))^((dof + 1) / 2), self excluded.
+    Returns a dict:
+      Z_raw = sum_ij w_ij, Z = max(Z_raw, float32(DBL_EPSILON));
+      rep[i, a] = sum_j w_ij^2 (y_i - y_j)_a, attr[i, a] = sum_e p_e w_ie (y_i - y_j)_a over the stored entries of row i;
+      grad = c (attr - rep / Z), c = 2 (dof + 1) / dof;
+      KL = sum_e p_e log(max(p_e, FLT_MIN) / max(float32(w_ie / Z), FLT_MIN));
+      A_rep, A_attr: the same sums as rep and attr over |.| of every term, W[i] = sum_j w_ij - what rounding errors scale with.
+    Dense, in chunks of targets."""
+    Y = np.asarray(Y, dtype=np.float32).astype(np.float64)
+    N, D = Y.shape
+    assert n_components is None or n_components == D
+    indptr = np.asarray(indptr, dtype=np.int64)
+    indices = np.asarray(indices, dtype=np.int64)[: indptr[-1]]
+    p = np.asarray(pval, dtype=np.float32).astype(np.float64)[: indptr[-1]]
+    dof = float(max(D - 1, 1))
+    expo = (dof + 1.0) / 2.0
+    c = 2.0 * (dof + 1.0) / dof
+    rep, A_rep, W = np.zeros((N, D)), np.zeros((N, D)), np.zeros(N)
+    for s in range(0, N, chunk):
+        e = min(N, s + chunk)
+        diff = Y[s:e, None, :] - Y[None, :, :]
+        w = dof / (dof + (diff * diff).sum(-1))
+        w = w if expo == 1.0 else (w * np.sqrt(w) if expo == 1.5 else w ** expo)
+        w[np.arange(e - s), np.arange(s, e)] = 0.0
+        W[s:e] = w.sum(1)
+        w2 = (w * w)[..., None]
+        rep[s:e] = (w2 * diff).sum(1)
+        A_rep[s:e] = (w2 * np.abs(diff)).sum(1)
+    Z_raw = float(W.sum())
+    Z = max(Z_raw, _TSNE_ZMIN)
+    rows = np.repeat(np.arange(N), np.diff(indptr))
+    dd = Y[rows] - Y[indices]
+    q = (dof / (dof + (dd * dd).sum(-1))) ** expo
+    attr, A_attr = np.zeros((N, D)), np.zeros((N, D))
+    for a in range(D):
+        attr[:, a] = np.bincount(rows, weights=p * q * dd[:, a], minlength=N)
+        A_attr[:, a] = np.bincount(rows, weights=p * q * np.abs(dd[:, a]), minlength=N)
+    KL = _tsne_kl_terms(p, q, Z)
+    return dict(Z_raw=Z_raw, Z=Z, rep=rep, attr=attr, grad=c * (attr - rep / Z), KL=KL, A_rep=A_rep, A_attr=A_attr, W=W, c=c, sum_p=float(p.sum()))
+
+
+def tsne_step(Y, update, gains, grad, momentum, lr, min_gain=0.01):
+    """One iteration of _gradient_descent's update rule as k_tsne_step applies it: the gain grows by 0.2f where update and
+    gradient disagree in sign and shrinks by 0.8f elsewhere (update == 0 included), floored at min_gain, all in float32; the
+    update momentum * update - lr * grad * gain in f64; the position float32(float64(y) + update).
+    Returns (Y_out f32, update f64, gains f32, grad * gain f64)."""
+    Y = np.asarray(Y, dtype=np.float32)
+    u = np.asarray(update, dtype=np.float64)
+    g = np.asarray(grad, dtype=np.float64)
+    gain = np.asarray(gains, dtype=np.float32)
+    inc = u * g < 0.0
+    gain = np.where(inc, gain + np.float32(0.2), gain * np.float32(0.8)).astype(np.float32)
+    gain = np.maximum(gain, np.float32(min_gain))
+    gg = g * gain.astype(np.float64)
+    u = momentum * u - lr * gg
+    return (Y.astype(np.float64) + u).astype(np.float32), u, gain, gg
