@@ -577,6 +577,29 @@ int vcy_tsne_step(const float *Y, float *Y_out, const int64_t *indptr, const int
                   float *gains, double *stats, void *workspace, int64_t N, int n_components, double momentum, double learning_rate,
                   double min_gain, int compute_error, vcy_stream stream);
 
+/* ---------------------------------------------------------------- upstream caller: PCA straight from CSR count layers
+ * perform_PCA on S_norm = log2(S_sz + pcount) (analysis.py:549-551, 678-700) where the layer only exists as CSR counts (the atlas
+ * path; the reference forms S_norm dense in float64).  A stored count c stands for x = log2(c * s + pcount) - log2(pcount), computed
+ * in f64 on the fly and never stored; s is the size factor of the element's CELL: scale[r] of its row (VCY_SCALE_ON_ROW: the CSR as
+ * stored, rows = cells) or scale[indices[p]] (VCY_SCALE_ON_INDEX: the gene-major copy, rows = genes, indices = cell numbers).
+ * vcy_csr_lognorm_spmm: out[r, j] = sum over the stored elements p of row r of x(p) * B[indices[p], j] for j < L; out (R, ldo) f64,
+ * B (N, ldb) f64, indptr int64 (R + 1) with indptr[R] == nnz, indices int32 in 0..N-1, data counts as VCY_U8 or VCY_U16 bits.
+ * vcy_csr_lognorm_stats: stats (R, 2) f64 = per row [sum x, sum x^2].
+ * Rows longer than vcy_csr_spmm_chunk() stored elements are summed in chunks of that length by separate waves and the partial sums
+ * added in chunk order: every sum has a fixed order, results are bit-identical from run to run (no atomics).  workspace:
+ * vcy_csr_spmm_workspace_bytes(nnz, L) bytes (L = 2 for the stats); may be NULL when that is 0.  max_row: an upper bound on the stored
+ * elements of any row, or 0 when not known; when it does not exceed the chunk length no row is cut, nothing but one wave per row is
+ * launched and the workspace may be NULL (a bound that is too small loses the elements of a row beyond it). */
+typedef enum { VCY_SCALE_ON_ROW = 0, VCY_SCALE_ON_INDEX = 1 } vcy_scale_on;
+int64_t vcy_csr_spmm_chunk(void);
+size_t vcy_csr_spmm_workspace_bytes(int64_t nnz, int64_t L);
+int vcy_csr_lognorm_spmm(const int64_t *indptr, const int32_t *indices, const void *data, const double *scale, const double *B,
+                         double *out, void *workspace, int64_t R, int64_t N, int64_t nnz, int64_t max_row, int64_t L, int64_t ldb,
+                         int64_t ldo, double pcount, int scale_on, int count_dtype, vcy_stream stream);
+int vcy_csr_lognorm_stats(const int64_t *indptr, const int32_t *indices, const void *data, const double *scale, double *stats,
+                          void *workspace, int64_t R, int64_t N, int64_t nnz, int64_t max_row, double pcount, int scale_on,
+                          int count_dtype, vcy_stream stream);
+
 /* ---------------------------------------------------------------- host helper: neighbour sampling of estimate_transition_prob
  * analysis.py:1561-1564 draws, per cell, np.random.choice(n, size, replace=False, p=p) from numpy's legacy global RNG.  This is
  * RandomState.choice(replace=False, p) restated over a pool of uniforms the caller drew from the same RandomState in one call

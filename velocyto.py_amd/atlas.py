@@ -379,6 +379,17 @@ def size_factors(totS: torch.Tensor, totU: torch.Tensor, C: int) -> Tuple[torch.
     return (sums[0] / C) / totS.clamp(min=1.0), (sums[1] / C) / totU.clamp(min=1.0)
 
 
+def pca_from_counts(cS: ops.CsrCounts, fS: torch.Tensor, n_components: int = 30, pcount: float = 1.0):
+    """The kNN space of the path from its own input: perform_PCA on S_norm = log2(S_sz + pcount) (analysis.py:549-551, 678-700)
+    straight from the rank's CSR counts and size factors (preprocess.DevicePCA.fit_transform_csr; cells sharded as in AtlasPath,
+    the per-pass sums all-reduced).  Returns (pcs_own, pca): the scores of the rank's own cells as a contiguous device tensor
+    (nloc, n_components) float64 - what AtlasPath(pcs=...) takes - and the fitted DevicePCA (the same on every rank)."""
+    from .preprocess import DevicePCA
+    pca = DevicePCA(n_components=n_components, svd_solver="subspace")
+    pcs = pca.fit_transform_csr(cS, fS, pcount=pcount)
+    return pcs.contiguous(), pca
+
+
 def auto_block_cells(nloc: int, C: int, G: int, dev, elem_bytes: int = 4) -> int:
     """Cells per streamed block chosen from the free HBM: as many as fit beside the CSR layers - a block holds ~2.6 dense
     rows per cell (Sx + the e rows it reads outside itself, Ux) of `elem_bytes` per element; the kNN workspace of 8192 queries x C

@@ -235,7 +235,7 @@ class CsrCounts:
     analysis.py:59-61, 240 GB).  ``slabptr`` is the per-row table of gene-slab boundaries the pooling kernel walks
     (vcy_csr_slab_ptr), built on first use."""
 
-    __slots__ = ("indptr", "indices", "data", "G", "_slabptr", "_nnz", "_istore", "_dstore")
+    __slots__ = ("indptr", "indices", "data", "G", "_slabptr", "_nnz", "_istore", "_dstore", "_max_row")
 
     def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, G: int):
         assert indptr.dtype == torch.int64 and indices.dtype == torch.int32 and data.dtype in (torch.uint8, torch.int16)
@@ -250,11 +250,19 @@ class CsrCounts:
             indices, data = self._istore[: self._nnz], self._dstore[: self._nnz]
         self.indptr, self.indices, self.data, self.G = indptr.contiguous(), indices, data, int(G)
         self._slabptr = None
+        self._max_row = None
 
     C = property(lambda self: int(self.indptr.numel()) - 1)
     nnz = property(lambda self: self._nnz)
     code = property(lambda self: U8 if self.data.dtype == torch.uint8 else U16)
     nbytes = property(lambda self: self.indptr.numel() * 8 + self.indices.numel() * 4 + self.data.numel() * self.data.element_size())
+
+    @property
+    def max_row(self) -> int:
+        """Stored elements of the longest row (one host read, then kept): tells the CSR products whether any row is cut into chunks."""
+        if self._max_row is None:
+            self._max_row = int((self.indptr[1:] - self.indptr[:-1]).max()) if self.C else 0
+        return self._max_row
 
     @property
     def slabptr(self) -> torch.Tensor:
@@ -334,6 +342,159 @@ class CsrCounts:
         cs = torch.zeros(self.nnz + 1, dtype=torch.int64, device=self.indptr.device)
         torch.cumsum(vals, 0, out=cs[1:])
         return (cs[self.indptr[1:]] - cs[self.indptr[:-1]]).double()
+
+    def transposed(self, block_nnz: int = 1 << 25) -> "CsrCounts":
+        """The gene-major copy: a CsrCounts of shape (G, C) whose rows are genes and whose indices are cell numbers, ascending
+        inside a gene (the operand of the contraction over the cells, ops.LogNormCsr).  Built once per fit, off the per-pass path."""
+        ptr, idx, dat = transpose_csr(self.indptr, self.indices, self.data, self.G, block_nnz)
+        return CsrCounts(ptr, idx, dat, self.C)
+
+
+def transpose_csr(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, G: int, block_nnz: int = 1 << 25):
+    """(indptr, indices, data) of a (C, G) CSR with sorted rows -> the same of its (G, C) transpose, rows sorted.  Index plumbing
+    on whatever device the tensors live on, in blocks of whole rows holding about `block_nnz` stored elements (the sort
+    temporaries stay small beside a 12-14 GB layer): a counting pass gives every gene its range; then, block by block, the block's
+    elements are sorted by (gene, cell) and appended to their genes' ranges behind what earlier blocks put there - blocks are
+    taken in ascending cell order, so the cells of a gene come out ascending."""
+    dev = indptr.device
+    C, nnz = int(indptr.numel()) - 1, int(indices.numel())
+    hp = indptr.cpu()
+    bounds = [0]                                                  # row blocks: as many whole rows as stay within block_nnz (at least one)
+    while bounds[-1] < C:
+        r0 = bounds[-1]
+        r1 = int(torch.searchsorted(hp, hp[r0] + int(block_nnz), right=True)) - 1
+        bounds.append(min(C, max(r1, r0 + 1)))
+    counts = torch.zeros(G, dtype=torch.int64, device=dev)
+    for r0, r1 in zip(bounds[:-1], bounds[1:]):
+        p0, p1 = int(hp[r0]), int(hp[r1])
+        if p1 > p0:
+            counts += torch.bincount(indices[p0:p1], minlength=G)
+    ptrT = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=ptrT[1:])
+    idxT = torch.empty(nnz, dtype=torch.int32, device=dev)
+    datT = torch.empty(nnz, dtype=data.dtype, device=dev)
+    cursor = ptrT[:-1].clone()                                    # next free position of every gene
+    for r0, r1 in zip(bounds[:-1], bounds[1:]):
+        p0, p1 = int(hp[r0]), int(hp[r1])
+        if p1 == p0:
+            continue
+        nb = r1 - r0
+        g = indices[p0:p1].long()
+        cell = torch.repeat_interleave(torch.arange(nb, device=dev), indptr[r0 + 1:r1 + 1] - indptr[r0:r1])
+        key, perm = torch.sort(g * nb + cell)                     # keys are distinct: (gene, cell) order
+        gs = torch.div(key, nb, rounding_mode="floor")
+        bc = torch.bincount(gs, minlength=G)
+        first = torch.cumsum(bc, 0) - bc                          # where a gene's run starts in the sorted block
+        dest = cursor[gs] + (torch.arange(p1 - p0, device=dev) - first[gs])
+        idxT[dest] = (key - gs * nb + r0).to(torch.int32)
+        datT[dest] = data[p0:p1][perm]
+        cursor += bc
+    return ptrT, idxT, datT
+
+
+SCALE_ON = {"row": 0, "index": 1}
+
+
+def _f64_vec(v, n: int, dev) -> torch.Tensor:
+    t = (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()
+    assert t.numel() == n, (t.numel(), n)
+    return t
+
+
+def _csr_workspace(counts: CsrCounts, L: int) -> Optional[torch.Tensor]:
+    """Room for the partial sums of rows longer than a chunk; none when the layer has no such row (max_row is handed to the kernel)."""
+    if counts.max_row <= int(_lib.lib().vcy_csr_spmm_chunk()):
+        return None
+    n = int(_lib.lib().vcy_csr_spmm_workspace_bytes(counts.nnz, L))
+    return torch.empty(n // 8, dtype=torch.float64, device=counts.indptr.device) if n else None
+
+
+def csr_lognorm_spmm(counts: CsrCounts, scale, B: torch.Tensor, *, scale_on: str = "row", pcount: float = 1.0,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r, :] = sum over the stored elements p of row r of x(p) * B[indices[p], :] with x = log2(count * s + pcount) - log2(pcount)
+    (vcy_csr_lognorm_spmm; f64, fixed summation order).  ``scale_on="row"``: s = scale[r] (the layer as stored: rows are cells);
+    ``"index"``: s = scale[indices[p]] (its gene-major copy, CsrCounts.transposed).  B (counts.G, L) float64 with unit column stride."""
+    if scale_on not in SCALE_ON:
+        raise ValueError(f"scale_on must be 'row' or 'index', got {scale_on!r}")
+    dev = counts.indptr.device
+    assert B.dtype == torch.float64 and B.is_cuda and B.dim() == 2 and B.shape[0] == counts.G, "B: (counts.G, L) float64 on the device"
+    R, L = counts.C, int(B.shape[1])
+    if L < 1:
+        raise ValueError("B needs at least one column")
+    if B.stride(1) != 1 or (B.shape[0] > 1 and B.stride(0) < L):
+        B = B.contiguous()
+    sc = _f64_vec(scale, R if scale_on == "row" else counts.G, dev)
+    if out is None:
+        out = torch.empty((R, L), dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and out.is_cuda and tuple(out.shape) == (R, L) and out.stride(1) == 1 and (R <= 1 or out.stride(0) >= L)
+    if R == 0:
+        return out
+    ws = _csr_workspace(counts, L)
+    _lib.check(_lib.lib().vcy_csr_lognorm_spmm(counts.indptr.data_ptr(), counts._istore.data_ptr(), counts._dstore.data_ptr(), sc.data_ptr(),
+                                               B.data_ptr(), out.data_ptr(), _p(ws), R, counts.G, counts.nnz, max(counts.max_row, 1), L, B.stride(0) if B.shape[0] > 1 else L,
+                                               out.stride(0) if R > 1 else L, float(pcount), SCALE_ON[scale_on], counts.code, _stream()),
+               "csr_lognorm_spmm")
+    return out
+
+
+def csr_lognorm_stats(countsT: CsrCounts, scale, pcount: float = 1.0, scale_on: str = "index") -> torch.Tensor:
+    """(2, R) float64: per row of `countsT` the sum of x and of x^2, x as in csr_lognorm_spmm (vcy_csr_lognorm_stats).  On the
+    gene-major copy (the default ``scale_on="index"``) these are the per-gene moments over the cells."""
+    if scale_on not in SCALE_ON:
+        raise ValueError(f"scale_on must be 'row' or 'index', got {scale_on!r}")
+    dev = countsT.indptr.device
+    R = countsT.C
+    sc = _f64_vec(scale, R if scale_on == "row" else countsT.G, dev)
+    st = torch.empty((R, 2), dtype=torch.float64, device=dev)
+    if R:
+        ws = _csr_workspace(countsT, 2)
+        _lib.check(_lib.lib().vcy_csr_lognorm_stats(countsT.indptr.data_ptr(), countsT._istore.data_ptr(), countsT._dstore.data_ptr(), sc.data_ptr(),
+                                                    st.data_ptr(), _p(ws), R, countsT.G, countsT.nnz, max(countsT.max_row, 1), float(pcount), SCALE_ON[scale_on], countsT.code,
+                                                    _stream()), "csr_lognorm_stats")
+    return st.T.contiguous()
+
+
+class LogNormCsr:
+    """The (C cells, G genes) operand X = log2(counts * scale[:, None] + pcount) - log2(pcount) of a PCA from CSR counts, never
+    formed: zero where nothing is stored, so both thin products the subspace iteration needs are sparse x thin-dense products over
+    the stored elements (csrc/csr_pca.hip).  Holds the layer and its gene-major copy (built here, once)."""
+
+    def __init__(self, counts: CsrCounts, scale, pcount: float = 1.0):
+        if not pcount > 0:
+            raise ValueError("pcount must be positive")
+        self.counts, self.pcount = counts, float(pcount)
+        self.scale = _f64_vec(scale, counts.C, counts.indptr.device)
+        self.countsT = counts.transposed()
+        self._stats = None
+
+    C = property(lambda self: self.counts.C)
+    G = property(lambda self: self.counts.G)
+
+    def project(self, Z: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """X Z: (G, l) -> (C, l), the thin projection over the genes."""
+        return csr_lognorm_spmm(self.counts, self.scale, Z, scale_on="row", pcount=self.pcount, out=out)
+
+    def contract(self, Y: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """X^T Y: (C, l) -> (G, l), the thin contraction over the cells."""
+        return csr_lognorm_spmm(self.countsT, self.scale, Y, scale_on="index", pcount=self.pcount, out=out)
+
+    def _moments(self) -> torch.Tensor:
+        if self._stats is None:
+            self._stats = csr_lognorm_stats(self.countsT, self.scale, self.pcount)
+        return self._stats
+
+    def col_sums(self) -> torch.Tensor:
+        """Per gene, the sum of x over THIS operand's cells (a rank's shard in a sharded run: all-reduce it)."""
+        return self._moments()[0]
+
+    def col_sumsq(self) -> torch.Tensor:
+        """Per gene, the sum of x^2 over this operand's cells (per shard, as col_sums)."""
+        return self._moments()[1]
+
+    def col_means(self) -> torch.Tensor:
+        """Per gene, the mean of x over THIS operand's cells.  In a sharded run that is the mean of the rank's shard, not of the
+        dataset: all-reduce col_sums() and the cell counts instead, as DevicePCA.fit_transform_csr does."""
+        return self._moments()[0] / max(self.C, 1)
 
 
 def weight_rows_from_sorted_knn(idx_sorted: torch.Tensor, diag: float, dtype=None):

@@ -161,6 +161,16 @@ class DevicePCA:
             #  gemv takes 4.9 ms for this 30 000 x 50 product, more than the projection itself)
             ops.gemm_nt(X, CellMatrix.from_genes_major(Z, torch.float64), col_corr=(Z * mean[:, None]).sum(0), out=Ybuf[:, :Z.shape[1]])
             return ops.gram_tn(X, mean, Ybuf) if ldy == Z.shape[1] else ops.gram_tn(X, mean, Ybuf)[:, :Z.shape[1]]
+        w, comps = self._iterate(AtA, G, l, k, dev, stacklevel=4)
+        pcs = ops.gemm_nt(X, comps, col_corr=(comps * mean).sum(1))
+        self._set_subspace_fit(w, comps, mean, total_var, pcs, k, C, G)
+        return pcs.cpu().numpy()
+
+    def _iterate(self, AtA, G: int, l: int, k: int, dev, stacklevel: int = 3):
+        """The blocked subspace iteration proper, on any operand: AtA(Z) = A^T (A Z) for a (G, l) block.  Seeded start, passes until the
+        leading k Ritz values stop moving (relative `tol`), Rayleigh-Ritz, scikit-learn's sign convention.  Returns the l Ritz values
+        (descending, clamped at 0) and the (k, G) components; sets converged_ and n_iter_.  `stacklevel`: frames from the warning of a
+        stopped iteration up to the public method's caller."""
         gen = torch.Generator(device=dev).manual_seed(int(self.random_state))
         Z = torch.linalg.qr(torch.randn((G, l), generator=gen, device=dev, dtype=torch.float64))[0]
         prev = None
@@ -178,14 +188,16 @@ class DevicePCA:
             import warnings
             warnings.warn(f"DevicePCA: subspace iteration stopped at max_iter={self.max_iter} before the leading {k} Ritz values settled to "
                           f"rel tol {self.tol:g} (clustered spectrum?); components_ may be unconverged - raise max_iter or use the exact route "
-                          "(svd_solver='full')", RuntimeWarning, stacklevel=2)
+                          "(svd_solver='full')", RuntimeWarning, stacklevel=stacklevel)
         W = AtA(Z)
         w, V = torch.linalg.eigh(Z.T @ W)
         w, V = w.flip(0).clamp_(min=0.0), V.flip(1)
         comps = (Z @ V[:, :k]).T.contiguous()                                   # (k, G)
         idx = comps.abs().argmax(1)
         comps = comps * torch.sign(comps[torch.arange(k, device=dev), idx])[:, None]     # sklearn's svd_flip
-        pcs = ops.gemm_nt(X, comps, col_corr=(comps * mean).sum(1))
+        return w, comps
+
+    def _set_subspace_fit(self, w, comps, mean, total_var: float, pcs, k: int, C: int, G: int) -> None:
         self.components_ = comps.cpu().numpy()
         self.explained_variance_ = (w[:k] / (C - 1)).cpu().numpy()
         self.explained_variance_ratio_ = self.explained_variance_ / total_var
@@ -194,7 +206,48 @@ class DevicePCA:
         self.n_components_, self.n_samples_, self.n_features_in_ = k, C, G
         self.noise_variance_ = float((total_var - self.explained_variance_.sum()) / max(1, min(C, G) - k))
         self._pcs_dev = pcs
-        return pcs.cpu().numpy()
+
+    def fit_transform_csr(self, counts: "ops.CsrCounts", scale, pcount: float = 1.0, group=None) -> torch.Tensor:
+        """PCA of S_norm = log2(counts * scale[:, None] + pcount) straight from a CSR count layer (cells x genes; `scale` the cells'
+        size factors), the matrix never formed: the same subspace iteration as the dense route with its two products taken over the
+        stored elements only (ops.LogNormCsr -> vcy_csr_lognorm_spmm; the operand is S_norm - log2(pcount), zero wherever nothing is
+        stored, and the centring removes the constant).  Always the subspace route: with l = min(C, G) columns it is exact.
+        Fitted attributes as `fit_transform`; returns the scores of the given cells as a DEVICE tensor (C_own, n_components) float64.
+
+        With `group` given, or a default process group of more than one rank, `counts` / `scale` are the rank's own cells
+        (distributed.shard_bounds): the contraction over the cells, the per-gene moments and the column sums are all-reduced
+        ((G + 1) x l doubles per pass), every rank ends with the same components_ and the scores of its own cells."""
+        from . import distributed as D
+        dev = counts.indptr.device
+        op = ops.LogNormCsr(counts, scale, pcount)
+        sharded = group is not None or D.active()
+        G = op.G
+        facts = torch.cat([op.col_sums(), op.col_sumsq(), torch.tensor([float(op.C)], dtype=torch.float64, device=dev)])
+        if sharded:
+            D.all_reduce_sum(facts, group)
+        C = int(round(float(facts[-1])))
+        k = min(C, G) if self.n_components is None else int(self.n_components)
+        if not 1 <= k <= min(C, G):
+            raise ValueError(f"n_components={self.n_components!r} must be between 1 and min(n_samples, n_features)={min(C, G)}")
+        l = min(min(C, G), k + 20)
+        mean = facts[:G] / C                                                    # of the operand: S_norm's mean less log2(pcount)
+        total_var = float((facts[G:2 * G].sum() - C * (mean * mean).sum()) / (C - 1))
+        Ybuf = torch.empty((op.C, l), dtype=torch.float64, device=dev)
+        Wbuf = torch.empty((G + 1, l), dtype=torch.float64, device=dev)
+
+        def AtA(Z):                                                             # A^T (A Z), A = X - 1 mean^T, centring as algebra
+            Y = op.project(Z, out=Ybuf)                                         # X Z - 1 (mean^T Z): the rank's own cells
+            Y -= (mean @ Z)[None, :]
+            op.contract(Y, out=Wbuf[:G])                                        # X^T Y - mean (1^T Y), summed over the ranks
+            Wbuf[G] = Y.sum(0)
+            if sharded:
+                D.all_reduce_sum(Wbuf, group)
+            return Wbuf[:G] - mean[:, None] * Wbuf[G][None, :]
+        w, comps = self._iterate(AtA, G, l, k, dev, stacklevel=3)
+        pcs = op.project(comps.T.contiguous())
+        pcs -= (comps @ mean)[None, :]
+        self._set_subspace_fit(w, comps, mean + float(np.log2(pcount)), total_var, pcs, k, C, G)
+        return pcs
 
     def __getstate__(self):
         return {k: v for k, v in self.__dict__.items() if k != "_pcs_dev"}      # checkpoints carry host arrays only
