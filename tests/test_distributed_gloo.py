@@ -281,3 +281,99 @@ def test_self_check_row_width_is_a_collective_decision():
     for rank, res, m in got:
         assert res["all_to_all_halo_sizes"] == "ok" and all(res["agreed"].values()), (rank, res)
         assert m == 1.5 * (world - 1)
+
+
+def _domain_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import velocyto_amd
+        from velocyto_amd import distributed as D
+        res = {}
+        # the last rank holds the odd value (rank 0 would win a MAX that simply kept its own operand on a NaN)
+        for name, odd, rest in (("nan", float("nan"), 1.0), ("huge", 1e39, 1.0), ("fine", 1e37, 1e37)):
+            val = odd if rank == world - 1 else rest
+            mine = torch.tensor([val], dtype=torch.float64)
+            try:
+                D.check_f64_sqrt_domain(mine)
+                res[name] = None
+            except ValueError as e:
+                res[name] = str(e)
+            res[name + "_untouched"] = float(mine) == val or (val != val and bool(torch.isnan(mine).all()))      # the caller's tensor is not written
+            # nobody was left behind in the reduce: the next collective completes with every rank in it
+            res[name + "_sum"] = float(D.all_reduce_sum(torch.ones(1, dtype=torch.float64)))
+        q.put((rank, res))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_collective_f64_sqrt_domain_check(world):
+    """distributed.check_f64_sqrt_domain: one rank's NaN or out-of-range maximum makes EVERY rank raise the ValueError (a NaN does
+    not survive a MAX all-reduce in any defined way: it goes in as +inf), values inside the range raise nowhere, and in each case all
+    ranks meet again in the next collective."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_domain_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = dict(q.get(timeout=120) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert sorted(got) == list(range(world))
+    for rank, res in got.items():
+        assert res["nan"] is not None and "outside the supported range" in res["nan"], (rank, res)
+        assert res["huge"] is not None and "outside the supported range" in res["huge"] and "1e+39" in res["huge"], (rank, res)
+        assert res["fine"] is None, (rank, res)
+        assert all(res[n + "_sum"] == world and res[n + "_untouched"] for n in ("nan", "huge", "fine")), (rank, res)
+
+
+def _compact_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import velocyto_amd
+        from velocyto_amd import distributed as D
+        C = 37
+        rng = np.random.default_rng(5)                        # the same "dataset" on every rank
+        data = {"float64": rng.normal(size=(C, 7)), "int16": rng.integers(-30000, 30000, (C, 6)).astype(np.int16)}
+        need = torch.as_tensor(np.random.default_rng(100 + rank).random(C) < 0.4)      # a rank-specific random mask
+        c0, c1 = D.shard_bounds(C, world, rank)
+        need[c0:c1] = True
+        plan = D.HaloPlan(need, C)
+        ok = plan.n_recv == int(need.sum()) - (c1 - c0)
+        for name, a in data.items():
+            local = torch.as_tensor(a[c0:c1])
+            full = torch.zeros((C,) + a.shape[1:], dtype=local.dtype)
+            if name == "int16":                               # (the transport moves no 16-bit elements: the same rows as 32-bit words)
+                plan.exchange(local.view(torch.int32), full.view(torch.int32))
+            else:
+                plan.exchange(local, full)
+            got = plan.compact(local)
+            ok = ok and got.dtype == local.dtype and got.is_contiguous() and tuple(got.shape) == (c1 - c0 + plan.n_recv, a.shape[1])
+            ok = ok and torch.equal(got, torch.cat([full[c0:c1], full[plan.recv_idx]])) and torch.equal(got, torch.as_tensor(a)[torch.cat([torch.arange(c0, c1), plan.recv_idx])])
+        q.put((rank, bool(ok), plan.n_recv))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_halo_plan_compact_buffer(world):
+    """HaloPlan.compact: the [own | halo] buffer holds the rows exchange() puts into a full-height buffer, taken at the rank's block
+    and at recv_idx - for f64 rows and for 16-bit rows (which travel as 32-bit words)."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_compact_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = [q.get(timeout=120) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert sorted(r for r, _, _ in got) == list(range(world)) and all(ok for _, ok, _ in got), got
+    assert sum(n for _, _, n in got) > 0                      # some rows did travel

@@ -1060,6 +1060,93 @@ def test_coldeltacor_partial_fused_dual(ops, dtype):
     assert eq(r1, f1) and eq(r2, f2)                             # same kernel, d[c] staged from dmat or evaluated on the fly
 
 
+WIDE_SHAPES = [(64, 70, 257), (500, 96, 700)]      # (G, C, nr): one column past a 256-column tile, and three tiles; C above the grouped kernel's minimum
+_wide_cache = {}
+
+
+def _wide_problem(ops, G, C, nr, dtype):
+    """Inputs of the wide-list tests, made once per shape and dtype and never written: pooled-like Sx / Ux, gammas and offsets, a
+    control, the chain's dmat, and unsorted neighbour lists with duplicates."""
+    key = (G, C, nr, dtype)
+    if key not in _wide_cache:
+        rng = np.random.default_rng(G + nr)
+        S = rng.gamma(2.0, 1.0, (G, C)) * (rng.random((G, C)) < 0.7)
+        U = rng.gamma(1.0, 1.0, (G, C)) * (rng.random((G, C)) < 0.6)
+        Sx, Ux, D2 = (ops.CellMatrix.from_genes_major(a, dtype) for a in (S, U, rng.normal(size=(G, C))))
+        gam = torch.as_tensor(rng.gamma(2.0, 0.3, G), dtype=torch.float32)
+        q = torch.as_tensor(rng.gamma(1.0, 0.05, G), dtype=torch.float32)
+        dmat = ops.velocity_chain(Sx, Ux, gam, q, want=("dmat",), transform=ops.SQRT, psc=1e-10)["dmat"]
+        _wide_cache[key] = (Sx, Ux, D2, gam, q, dmat, rng.integers(0, C, (C, nr)))
+    return _wide_cache[key]
+
+
+def _bits_equal(a, b):
+    return torch.equal(torch.nan_to_num(a, nan=7.0), torch.nan_to_num(b, nan=7.0))
+
+
+def _wide_schedule_and_presorted(call, full, dtype):
+    """What every wide-list entry point owes its caller besides the values: a schedule over every second cell leaves the odd rows of
+    the prefilled outputs untouched and gives the even rows the full call's values (within CORR_ATOL: half the cells may take the
+    other kernel, another summation order), and saying `presorted=False` gives the bits of looking (`None`)."""
+    C = full[0].shape[0]
+    outs = [torch.full_like(f, v) for f, v in zip(full, (7.0, 9.0))]
+    call(order=torch.arange(0, C, 2, dtype=torch.int32), outs=outs)
+    for o, f, v in zip(outs, full, (7.0, 9.0)):
+        assert bool((o[1::2] == v).all())
+        m = ~torch.isnan(f[0::2])
+        assert torch.allclose(o[0::2][m], f[0::2][m], atol=CORR_ATOL[dtype], rtol=0)
+    said = call(presorted=False)
+    assert all(_bits_equal(a, b) for a, b in zip(said, full))
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("G,C,nr", WIDE_SHAPES)
+def test_coldeltacor_partial_fused_wide_lists(ops, G, C, nr, dtype):
+    """nrndm > 256 through the fused entry point: the sort / launch / scatter-back path returns what velocity_chain followed by
+    coldeltacor_partial returns (itself held to the oracle in test_coldeltacor_partial_wide_lists_are_tiled), bit for bit."""
+    Sx, Ux, _, gam, q, dmat, ixs = _wide_problem(ops, G, C, nr, dtype)
+    ref = ops.coldeltacor_partial(Sx, dmat, ixs, ops.SQRT, ops.RULES_PARTIAL, 1e-10)
+
+    def call(order=None, outs=(None,), presorted=None):
+        return (ops.coldeltacor_partial_fused(Sx, Ux, gam, q, ixs, ops.SQRT, ops.RULES_PARTIAL, 1e-10, order=order, out=outs[0], presorted=presorted),)
+    full = call()
+    assert _bits_equal(full[0], ref)
+    _wide_schedule_and_presorted(call, full, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("G,C,nr", WIDE_SHAPES)
+def test_coldeltacor_partial_dual_wide_lists(ops, G, C, nr, dtype):
+    """nrndm > 256 through the dual entry point == two single launches (the bounds of test_coldeltacor_partial_dual_equals_two_launches)."""
+    Sx, _, D2, _, _, dmat, ixs = _wide_problem(ops, G, C, nr, dtype)
+    refs = [ops.coldeltacor_partial(Sx, d, ixs, ops.SQRT, ops.RULES_PARTIAL, 1e-10) for d in (dmat, D2)]
+
+    def call(order=None, outs=(None, None), presorted=None):
+        return ops.coldeltacor_partial_dual(Sx, dmat, D2, ixs, ops.SQRT, ops.RULES_PARTIAL, 1e-10, order=order, out=outs[0], out_rndm=outs[1],
+                                            presorted=presorted)
+    full = call()
+    for x, y in zip(refs, full):
+        x, y = x.cpu().numpy(), y.cpu().numpy()
+        assert np.array_equal(np.isnan(x), np.isnan(y))
+        np.testing.assert_allclose(x[~np.isnan(x)], y[~np.isnan(y)], rtol=0, atol=2e-6 if dtype == "float32" else 1e-13)
+    _wide_schedule_and_presorted(call, full, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("G,C,nr", WIDE_SHAPES)
+def test_coldeltacor_partial_fused_dual_wide_lists(ops, G, C, nr, dtype):
+    """nrndm > 256 through the fused dual entry point == the dual one on the chain's dmat, bit for bit."""
+    Sx, Ux, D2, gam, q, dmat, ixs = _wide_problem(ops, G, C, nr, dtype)
+    refs = ops.coldeltacor_partial_dual(Sx, dmat, D2, ixs, ops.SQRT, ops.RULES_PARTIAL, 1e-10)
+
+    def call(order=None, outs=(None, None), presorted=None):
+        return ops.coldeltacor_partial_fused_dual(Sx, Ux, gam, q, D2, ixs, ops.SQRT, ops.RULES_PARTIAL, 1e-10, order=order, out=outs[0],
+                                                  out_rndm=outs[1], presorted=presorted)
+    full = call()
+    assert _bits_equal(full[0], refs[0]) and _bits_equal(full[1], refs[1])
+    _wide_schedule_and_presorted(call, full, dtype)
+
+
 def test_knn_search_segmented_equals_one_launch(ops, monkeypatch):
     """Point sets beyond one launch's candidate range are searched in segments and merged (ops._knn_search_segmented):
     same neighbours, same order (ties by index), same fp64 distances as the one-launch search."""

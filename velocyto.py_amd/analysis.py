@@ -595,28 +595,13 @@ class VelocytoLoom(PreprocessMixin):
         if kwargs:
             logging.warning(f"keyword arguments were passed but could not be interpreted {kwargs}")
         C = self.dev("S").C
-        if n_sight is None and n_neighbors is None:
-            n_neighbors = int(C / 5)
-        if (n_sight is not None) and (n_neighbors is not None) and n_neighbors != n_sight:
-            raise ValueError("n_sight and n_neighbors are different names for the same parameter, they cannot be set differently")
-        if n_sight is not None and n_neighbors is None:
-            n_neighbors = n_sight
-        if psc is None:
-            psc = 1.0 if transform in ("log", "logratio") else (1e-10 if transform == "sqrt" else 0)
-        if transform not in ("log", "logratio", "linear", "sqrt"):
-            raise NotImplementedError(f"transform={transform} is not a valid parameter")
-        if "pcs" in hidim:
-            raise NotImplementedError("hidim='pcs' (velocity in PCA space) is not on the accelerated path")
-        if ndims is not None:
-            raise ValueError(f"ndims was set to {ndims} but hidim != 'pcs'. Set ndims = None for hidim='{hidim}'")
+        n_neighbors, psc, mode, kern = stage_d_args(C, transform, hidim, ndims, n_sight, n_neighbors, psc)
         if knn_random:
             np.random.seed(random_seed)                                            # :1529
         hi = self.dev(hidim)
         dS = self.dev("delta_S")
         embedding = np.asarray(getattr(self, embed), dtype=np.float64)
         self.embedding = embedding
-        mode = {"linear": 0, "sqrt": 1, "log": 2, "logratio": 3}[transform]
-        kern = {"linear": ops.LINEAR, "sqrt": ops.SQRT, "log": ops.LOG10, "logratio": ops.LINEAR}[transform]
         # (uploaded before any kernel is queued: a host-to-device copy waits for what is ahead of it in the stream, and the host with it)
         emb_dev = torch.from_numpy(np.ascontiguousarray(embedding)).to(hi.t.device)
         # f32 sqrt with a negligible pseudocount on a matrix of ordinary scale: the three-instruction form (decided from
@@ -644,9 +629,7 @@ class VelocytoLoom(PreprocessMixin):
         if knn_random:
             self.corr_calc = "knn_random"
             n_cand = int(knn_ix.shape[1])
-            p = np.linspace(sampling_probs[0], sampling_probs[1], n_cand)
-            p = p / p.sum()
-            size = int(sampled_fraction * (n_neighbors + 1))
+            p, size = sampling_plan(sampling_probs, n_cand, sampled_fraction, n_neighbors)
             dev = hi.t.device
             self.__dict__.pop("embedding_knn", None)
             sched = ops.hilbert_order(emb_dev) if embedding.shape[1] >= 2 else None        # scheduling only: same numbers in any order
@@ -703,12 +686,9 @@ class VelocytoLoom(PreprocessMixin):
             self.sampling_ixs = sampling_ixs
             self._neigh = neigh
             self._corr = corr
-            if ops.corr_fixup(self._corr, neigh, zero_self=True, fix_nan=True, nan_to=1.0):                      # :1604-1607
-                logging.warning("Nans encountered in corrcoef and corrected to 1s. If not identical cells were present it is probably a small isolated cluster converging after imputation.")
+            fix_correlations(corr, corr_r, neigh)                                                  # :1604-1607
             if calculate_randomized:
                 self._corr_random = corr_r
-                if ops.corr_fixup(self._corr_random, neigh, zero_self=True, fix_nan=True, nan_to=1.0):
-                    logging.warning("Nans encountered in corrcoef_random and corrected to 1s. If not identical cells were present it is probably a small isolated cluster converging after imputation.")
             else:
                 self.__dict__.pop("_corr_random", None)
         else:
@@ -729,36 +709,14 @@ class VelocytoLoom(PreprocessMixin):
         if self.corr_calc not in ("full", "knn_random"):
             raise NotImplementedError(f"Weird value self.corr_calc={self.corr_calc}")
         neigh = self._neigh
-        hi = self.dev(self.which_hidim)
-        dev = hi.t.device
-
-        order = self.__dict__.get("_embed_order") if self.corr_calc == "knn_random" else None
-        n = neigh.shape[1]
-        names = [("_corr", "delta_S")] + ([("_corr_random", "delta_S_rndm")] if "_corr_random" in self.__dict__ else [])
-        parts = []
-        for corr_name, _ in names:
-            corr = self.__dict__[corr_name]
-            c = corr if self.corr_calc == "knn_random" else torch.gather(corr, 1, neigh.long())
-            parts.append(ops.transition_prob(c.contiguous(), neigh, self.embedding, sigma_corr))       # (tp, P - knn/n, delta_embedding)
-        scalings = [None] * len(names)
-        if expression_scaling:
-            # hi_dim @ (P - knn/n).T (:1716, and :1728 for the control) and the cosine projection of :1717 / :1729.  One launch
-            # (vcy_embedding_scaling): groups of schedule-adjacent cells gather the rows of their common neighbours once, the
-            # (genes, cells) estimates stay in registers.  Lists wider than it sorts in one workgroup take the two-step route.
-            dS_r = self.dev(names[1][1]) if len(names) == 2 else None
-            cos = ops.embedding_scaling(hi, self.dev(names[0][1]), neigh, parts[0][1], dS_r, parts[1][1] if len(names) == 2 else None, order=order,
-                                        validate=False)
-            if cos is None:
-                indptr = torch.arange(0, (neigh.shape[0] + 1) * n, n, dtype=torch.int64, device=dev)
-                if len(names) == 2:
-                    estims = ops.knn_pool_w2(hi, indptr, neigh.reshape(-1), parts[0][1].reshape(-1), parts[1][1].reshape(-1), validate=False, order=order)
-                else:
-                    estims = (ops.knn_pool(hi, indptr, neigh.reshape(-1), parts[0][1].reshape(-1), validate=False, order=order),)
-                cos = [ops.row_cosproj(self.dev(dS_name), estims[i]) for i, (_, dS_name) in enumerate(names)]                # :1717
-                del estims
-            for i in range(len(names)):
-                scalings[i] = torch.clamp(cos[i] / scaling_penalty, 0, 1)                              # NaN stays NaN, like np.clip
-        res = [(tp, de if sc is None else de * sc[:, None], sc) for (tp, _, de), sc in zip(parts, scalings)]
+        full = self.corr_calc == "full"
+        corrs = [self.__dict__["_corr"], self.__dict__.get("_corr_random")]
+        if full:
+            corrs = [None if c is None else torch.gather(c, 1, neigh.long()) for c in corrs]
+        dS = self.dev("delta_S") if expression_scaling else None
+        dS_r = self.dev("delta_S_rndm") if expression_scaling and corrs[1] is not None else None
+        res = embedding_shift(self.dev(self.which_hidim), dS, dS_r, neigh, neigh, corrs[0], corrs[1], self.embedding, sigma_corr,
+                              expression_scaling, scaling_penalty, order=None if full else self.__dict__.get("_embed_order"))
 
         tp, de, sc = res[0]
         self._tp, self._tp_ixs = tp, neigh
@@ -922,6 +880,79 @@ class VelocytoLoom(PreprocessMixin):
             self.raw_S, self.raw_U, self.raw_A = layers["spliced"], layers["unspliced"], layers.get("ambiguous")
             self.raw_initial_cell_size, self.raw_initial_Ucell_size = self.raw_S.sum(0), self.raw_U.sum(0)
             self.raw_ca, self.raw_ra = dict(ca), dict(ra)
+
+
+_NAN_WARNING = ("Nans encountered in {} and corrected to 1s. If not identical cells were present it is probably a small isolated cluster "
+                "converging after imputation.")
+
+
+def stage_d_args(C: int, transform: str, hidim: str, ndims, n_sight, n_neighbors, psc):
+    """The argument resolution of estimate_transition_prob (analysis.py:1452-1535): (n_neighbors, psc, the delta_transform mode,
+    the kernel transform), or the reference's exception for a call it refuses."""
+    if n_sight is None and n_neighbors is None:
+        n_neighbors = int(C / 5)
+    if (n_sight is not None) and (n_neighbors is not None) and n_neighbors != n_sight:
+        raise ValueError("n_sight and n_neighbors are different names for the same parameter, they cannot be set differently")
+    if n_sight is not None and n_neighbors is None:
+        n_neighbors = n_sight
+    if psc is None:
+        psc = 1.0 if transform in ("log", "logratio") else (1e-10 if transform == "sqrt" else 0)
+    if transform not in ("log", "logratio", "linear", "sqrt"):
+        raise NotImplementedError(f"transform={transform} is not a valid parameter")
+    if "pcs" in hidim:
+        raise NotImplementedError("hidim='pcs' (velocity in PCA space) is not on the accelerated path")
+    if ndims is not None:
+        raise ValueError(f"ndims was set to {ndims} but hidim != 'pcs'. Set ndims = None for hidim='{hidim}'")
+    mode = {"linear": 0, "sqrt": 1, "log": 2, "logratio": 3}[transform]
+    kern = {"linear": ops.LINEAR, "sqrt": ops.SQRT, "log": ops.LOG10, "logratio": ops.LINEAR}[transform]
+    return n_neighbors, psc, mode, kern
+
+
+def sampling_plan(sampling_probs: Tuple[float, float], n_cand: int, sampled_fraction: float, n_neighbors: int):
+    """(p over the n_cand nearest, nearest first; number of neighbours drawn per cell)   (analysis.py:1552-1559)."""
+    p = np.linspace(sampling_probs[0], sampling_probs[1], n_cand)
+    return p / p.sum(), int(sampled_fraction * (n_neighbors + 1))
+
+
+def fix_correlations(corr: torch.Tensor, corr_random: Optional[torch.Tensor], neigh: torch.Tensor) -> None:
+    """analysis.py:1604-1607 on the compact correlations, in place: a cell's pair with itself to 0, NaN to 1 (with the warning)."""
+    for c, name in ((corr, "corrcoef"), (corr_random, "corrcoef_random")):
+        if c is not None and ops.corr_fixup(c, neigh, zero_self=True, fix_nan=True, nan_to=1.0):
+            logging.warning(_NAN_WARNING.format(name))
+
+
+def embedding_shift(e: CellMatrix, dS: Optional[CellMatrix], dS_rndm: Optional[CellMatrix], neigh_e: torch.Tensor, neigh_emb: torch.Tensor,
+                    corr: torch.Tensor, corr_rndm: Optional[torch.Tensor], embedding, sigma_corr: float, expression_scaling: bool,
+                    scaling_penalty: float, cell0: int = 0, order: Optional[torch.Tensor] = None):
+    """calculate_embedding_shift (analysis.py:1670-1733) in neighbour-list form for the cells cell0 .. cell0 + C_out - 1 of the
+    embedding: [(tp, delta_embedding, scaling or None)] for the real correlations and, when `corr_rndm` is given, the control.
+    `e`: the matrix whose rows `neigh_e` numbers, the cells themselves its first C_out rows; dS / dS_rndm in e's row shape (read
+    with expression_scaling only); `neigh_emb`: the same lists in the embedding's numbering."""
+    corrs = [corr] + ([corr_rndm] if corr_rndm is not None else [])
+    parts = [ops.transition_prob(c.contiguous(), neigh_emb, embedding, sigma_corr, cell0=cell0) for c in corrs]      # (tp, P - knn/n, delta_embedding)
+    dual = len(parts) == 2
+    scalings = [None] * len(parts)
+    if expression_scaling:
+        # hi_dim @ (P - knn/n).T (:1716, and :1728 for the control) and the cosine projection of :1717 / :1729.  One launch
+        # (vcy_embedding_scaling): groups of schedule-adjacent cells gather the rows of their common neighbours once, the
+        # (genes, cells) estimates stay in registers.  Lists wider than it sorts in one workgroup take the two-step route.
+        C_out, n = (int(x) for x in neigh_e.shape)
+        dSs = [dS, dS_rndm][:len(parts)]
+        cos = None
+        if C_out:
+            cos = ops.embedding_scaling(e, dS, neigh_e, parts[0][1], dS_rndm if dual else None, parts[1][1] if dual else None, order=order,
+                                        validate=False)
+        if cos is None:
+            indptr = torch.arange(0, (C_out + 1) * n, n, dtype=torch.int64, device=e.t.device)
+            if dual:
+                estims = ops.knn_pool_w2(e, indptr, neigh_e.reshape(-1), parts[0][1].reshape(-1), parts[1][1].reshape(-1), C_out=C_out,
+                                         validate=False, order=order)
+            else:
+                estims = (ops.knn_pool(e, indptr, neigh_e.reshape(-1), parts[0][1].reshape(-1), C_out=C_out, validate=False, order=order),)
+            cos = [ops.row_cosproj(m if m.C == C_out else CellMatrix(m.t[:C_out], m.G), est) for m, est in zip(dSs, estims)]      # :1717
+            del estims
+        scalings = [torch.clamp(c / scaling_penalty, 0, 1) for c in cos]                                   # NaN stays NaN, like np.clip
+    return [(tp, de if sc is None else de * sc[:, None], sc) for (tp, _, de), sc in zip(parts, scalings)]
 
 
 def markov_csr(tp: torch.Tensor, ixs: torch.Tensor, direction: str):

@@ -243,13 +243,7 @@ class AtlasPath:
                 abs_st = torch.tensor([0.0, float("inf"), 0.0], dtype=torch.float64, device=self._ebuf.t.device)
             stats = D.all_reduce_abs_stats(abs_st)
             if self.dtype == torch.float64:
-                # a rank that raised on its own block would leave the others waiting in the collectives: the fact is reduced first (MAX),
-                # then every rank takes the same decision
-                if absmax is None:
-                    absmax = torch.zeros(1, dtype=torch.float64, device=self._ebuf.t.device)
-                m = float(D.all_reduce_max(absmax))
-                if not m < ops.F64_SQRT_MAX:
-                    raise ValueError(f"colDeltaCor sqrt transform in f64: |e| reaches {m:.3g}, outside the supported range (< {ops.F64_SQRT_MAX:g})")
+                D.check_f64_sqrt_domain(torch.zeros(1, dtype=torch.float64, device=self._ebuf.t.device) if absmax is None else absmax)
             self.rules = ops.partial_rules_for(self._ebuf, ops.SQRT, self.psc, stats=stats, cells=self.C, domain_checked=True)
         ev[0].record()
         D.all_reduce_sum(mom)

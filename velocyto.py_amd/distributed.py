@@ -99,6 +99,17 @@ def all_reduce_max(t: torch.Tensor, group=None) -> torch.Tensor:
     return t
 
 
+def check_f64_sqrt_domain(absmax: torch.Tensor, group=None) -> None:
+    """The collective form of ops.check_f64_sqrt_domain: `absmax` is this rank's max |e| (one element, f64; zero for a rank without
+    rows).  A rank raising alone would leave the others waiting in the next collective, so the fact is reduced first (MAX) and every
+    rank takes the same decision.  MAX of a NaN is not defined (the ranks could see different results): a NaN goes in as +inf, and a
+    matrix holding one is refused on every rank.  Raises ops' ValueError ("... outside the supported range") on all ranks or none."""
+    from . import ops
+    m = float(all_reduce_max(torch.nan_to_num(absmax.double().reshape(1), nan=float("inf")), group))
+    if not m < ops.F64_SQRT_MAX:
+        raise ValueError(ops.F64_SQRT_DOMAIN_MSG.format(m, ops.F64_SQRT_MAX))
+
+
 def all_gather_rows(local: torch.Tensor, n_total: int, out: Optional[torch.Tensor] = None, group=None) -> torch.Tensor:
     """Reassemble a row-sharded (shard_bounds) tensor: local (n_loc, ...) -> (n_total, ...).
     Equal shards use one all_gather_into_tensor straight into `out`; ragged shards pad to the
@@ -252,6 +263,17 @@ class HaloPlan:
             packed = f[src] if total else f[:0]
             outs.append(all_to_all_uneven(packed, e_send, e_recv, group=self.group))
         return (lens_halo, *outs)
+
+    def compact(self, local: torch.Tensor) -> torch.Tensor:
+        """The compact [own | halo] buffer of a row tensor: (n_loc + n_recv, ...), the rank's rows first, then the halo rows in the
+        order localize() numbers them.  16-bit rows (count layers; an even row length) travel as 32-bit words."""
+        n_loc = self.c1 - self.c0
+        buf = torch.zeros((n_loc + self.n_recv,) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
+        buf[:n_loc] = local
+        if self.n_recv:
+            v = buf.view(torch.int32) if local.element_size() == 2 else buf
+            self.end(self.begin(v[:n_loc], recv_out=v[n_loc:]), v, row0=n_loc)
+        return buf
 
     def exchange(self, local: torch.Tensor, out_full: torch.Tensor) -> torch.Tensor:
         """local: (c1-c0, ld) rows this rank owns; out_full: (n_total, ld).  Afterwards out_full holds the

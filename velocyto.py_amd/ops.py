@@ -521,19 +521,10 @@ def knn_pool_csr(counts: CsrCounts, scale, indptr, indices, weights, dtype=None,
     dev = counts.indptr.device
     dt = resolve_dtype(dtype)
     C_out = counts.C - cell0 if C_out is None else C_out
-    ip = (indptr if isinstance(indptr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(indptr).astype(np.int64))).to(device=dev, dtype=torch.int64).contiguous()
-    ix = _as_i32(indices, dev)
-    w = (weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))).to(device=dev, dtype=dt).contiguous()
-    sc = (torch.ones(counts.C, dtype=torch.float64, device=dev) if scale is None else
-          (scale if isinstance(scale, torch.Tensor) else torch.as_tensor(np.asarray(scale, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous())
-    assert ip.numel() == C_out + 1 and ix.numel() == w.numel() and sc.numel() == counts.C
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= counts.C):
-        raise ValueError("neighbour index out of range")
+    ip, ix, (w,), order = _pool_args(dev, dt, counts.C, C_out, indptr, indices, (weights,), order, validate)
+    sc = _scale_vec(scale, counts.C, dev)
     out = CellMatrix.empty(C_out, counts.G, dt) if out is None else out
     assert out.C >= C_out and out.G == counts.G and out.dtype == dt
-    if order is not None:
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
-        assert order.numel() == C_out
     _lib.check(_lib.lib().vcy_knn_pool_csr(counts.indptr.data_ptr(), counts._istore.data_ptr(), counts._dstore.data_ptr(), counts.slabptr.data_ptr(),
                                            sc.data_ptr(), out.t.data_ptr(), ip.data_ptr(), ix.data_ptr(), w.data_ptr(), _p(order), counts.C, counts.G,
                                            out.ld, cell0, C_out, int(maximum), counts.code, out.code, _stream()), "knn_pool_csr")
@@ -561,20 +552,29 @@ def _as_i32(ixs, dev) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(ixs).astype(np.int32)).to(dev)
 
 
+def _pool_args(dev, dt, n_rows: int, C_out: int, indptr, indices, weights: Sequence, order, validate: bool):
+    """The graph arguments of the pooling entry points (numpy arrays or tensors) as contiguous tensors on `dev`: (indptr int64,
+    indices int32, the weight vectors in `dt`, order int32 or None).  `validate` range-checks the indices against the `n_rows` rows
+    of the pooled matrix (a device->host sync)."""
+    ip = (indptr if isinstance(indptr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(indptr).astype(np.int64))).to(device=dev, dtype=torch.int64).contiguous()
+    ix = _as_i32(indices, dev)
+    ws = tuple((w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w))).to(device=dev, dtype=dt).contiguous() for w in weights)
+    assert ip.numel() == C_out + 1 and all(w.numel() == ix.numel() for w in ws)
+    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= n_rows):
+        raise ValueError("neighbour index out of range")
+    if order is not None:
+        order = order.to(device=dev, dtype=torch.int32).contiguous()
+        assert order.numel() == C_out
+    return ip, ix, ws, order
+
+
+def _scale_vec(scale, n: int, dev) -> torch.Tensor:
+    """Per-cell size factors as f64 on the device; None = ones."""
+    return torch.ones(n, dtype=torch.float64, device=dev) if scale is None else _f64_vec(scale, n, dev)
+
+
 # --------------------------------------------------------------------------- stage D
 TILE_COLS = 256      # widest neighbour list one workgroup of the grouped kernel sorts in LDS (csrc/coldeltacor.hip)
-
-
-def _sorted_rows(ix: torch.Tensor, out: torch.Tensor, presorted: Optional[bool] = None):
-    """Lists wider than one tile are walked in column tiles; a pair's value does not depend on its column, so the rows are
-    sorted by neighbour index first (adjacent cells then meet the same rows in the same tile) and the results are put
-    back in the caller's column order.  Returns (ixs to launch with, (perm, sorted-order buffer) or None, caller's out).
-    presorted: None = look (reads a flag back: a device sync); True / False = the caller knows (no sync)."""
-    if ix.shape[1] <= TILE_COLS or (bool((ix[:, 1:] >= ix[:, :-1]).all()) if presorted is None else presorted):
-        return ix, None, out
-    srt, perm = torch.sort(ix, dim=1)
-    # the launch buffer starts as the caller's rows in sorted column order: rows the schedule does not name round-trip
-    return srt.contiguous(), (perm, out.gather(1, perm)), out
 
 
 def abs_stats(e: CellMatrix) -> torch.Tensor:
@@ -588,6 +588,7 @@ def abs_stats(e: CellMatrix) -> torch.Tensor:
 
 
 F64_SQRT_MAX = 1e38
+F64_SQRT_DOMAIN_MSG = "colDeltaCor sqrt transform in f64: |e| reaches {:.3g}, outside the supported range (< {:g})"
 
 
 def check_f64_sqrt_domain(e: CellMatrix) -> None:
@@ -595,11 +596,13 @@ def check_f64_sqrt_domain(e: CellMatrix) -> None:
     correctly rounded root in all but near-tie cases for arguments inside the f32 exponent range, NaN above 3.4e38 (the converted
     argument is +inf, v_rsq_f32 of it is 0, and inf * 0 is NaN).  A count-derived matrix never comes near it; a matrix that does is
     refused here (one reduction, one device->host sync - the callers that decide the branch rule once per matrix come through here,
-    ops.partial_rules_for; every `validate=True` call of the partial entry points, fused ones included, does too)."""
+    ops.partial_rules_for; every `validate=True` call of the partial entry points, fused ones included, does too).  A matrix that
+    holds NaN passes (`m >= MAX` is false for NaN) and gives the reference's NaN correlations; sharded callers, where every rank
+    must decide alike, use distributed.check_f64_sqrt_domain instead."""
     lo, hi = e.t.aminmax()
     m = max(abs(float(lo)), abs(float(hi)))
     if m >= F64_SQRT_MAX:
-        raise ValueError(f"colDeltaCor sqrt transform in f64: |e| reaches {m:.3g}, outside the supported range (< {F64_SQRT_MAX:g})")
+        raise ValueError(F64_SQRT_DOMAIN_MSG.format(m, F64_SQRT_MAX))
 
 
 def literal_rule_forced() -> bool:
@@ -640,6 +643,50 @@ def partial_rules_for(e: CellMatrix, transform: int, psc: float, stats: Optional
     return RULES_PARTIAL_NOPSC if (mean >= SCALE_ORDINARY and tiny >= 1e-20) else RULES_PARTIAL
 
 
+def _schedule(order, dev, C_out):
+    """(order as int32 on the device or None, number of scheduled cells): a schedule may name only SOME of the C_out cells (e.g. those
+    whose neighbours are all rank-local, while the halo exchange is still in flight); rows are addressed by cell id."""
+    if order is None:
+        return None, C_out
+    order = order.to(device=dev, dtype=torch.int32).contiguous()
+    assert int(order.numel()) <= C_out
+    return order, int(order.numel())
+
+
+def _partial_launch(what: str, launch, e, d_rows: int, d_row0: int, ixs, transform: int, cell0: int, order, outs, validate: bool,
+                    presorted: Optional[bool]):
+    """Everything the partial stage-D entry points share around their launch.  `e`: the matrix the lists index (its device, dtype
+    and row count; the f64 sqrt-domain check under `validate`); `d_rows` rows of d / Ux starting at cell `d_row0`; `outs`: one or
+    two caller's outputs or None (allocated here, returned as a tuple; rows the schedule does not name stay as they are).
+    `launch(ix, outs, order, n_sched)` makes the library call with the lists and outputs it is handed and returns its code.
+
+    Lists wider than one tile are walked in column tiles; a pair's value does not depend on its column, so the rows are sorted by
+    neighbour index first (adjacent cells then meet the same rows in the same tile) and the results are put back in the caller's
+    column order.  presorted: None = look (reads a flag back: a device sync); True / False = the caller knows (no sync)."""
+    dev = e.t.device
+    ix = _as_i32(ixs, dev)
+    C_out, nrndm = ix.shape
+    assert d_row0 <= cell0 and cell0 + C_out <= d_row0 + d_rows
+    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= e.C):
+        raise ValueError("neighbour index out of range")
+    if validate and transform == SQRT and e.dtype == torch.float64 and e.C:
+        check_f64_sqrt_domain(e)
+    outs = tuple(torch.empty((C_out, nrndm), dtype=e.dtype, device=dev) if o is None else o for o in outs)
+    order, n_sched = _schedule(order, dev, C_out)
+    if n_sched == 0:
+        return outs
+    if nrndm <= TILE_COLS or (bool((ix[:, 1:] >= ix[:, :-1]).all()) if presorted is None else presorted):
+        _lib.check(launch(ix, outs, order, n_sched), what)
+        return outs
+    srt, perm = torch.sort(ix, dim=1)
+    # the launch buffers start as the caller's rows in sorted column order: rows the schedule does not name round-trip
+    bufs = tuple(o.gather(1, perm) for o in outs)
+    _lib.check(launch(srt.contiguous(), bufs, order, n_sched), what)
+    for o, buf in zip(outs, bufs):
+        o.scatter_(1, perm, buf)
+    return outs
+
+
 def coldeltacor_partial(e: CellMatrix, d: CellMatrix, ixs, transform: int, rules: int = RULES_PARTIAL, psc: float = 0.0,
                         cell0: int = 0, order: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                         d_row0: int = 0, validate: bool = True, presorted: Optional[bool] = None) -> torch.Tensor:
@@ -647,71 +694,27 @@ def coldeltacor_partial(e: CellMatrix, d: CellMatrix, ixs, transform: int, rules
     `d` may hold only the rows of cells d_row0.. (cell-sharded runs); `validate` range-checks ixs
     (a device->host sync; hot loops that built ixs themselves pass False)."""
     assert e.ld == d.ld and e.dtype == d.dtype and e.G == d.G
-    ix = _as_i32(ixs, e.t.device)
-    C_out, nrndm = ix.shape
-    assert d_row0 <= cell0 and cell0 + C_out <= d_row0 + d.C
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= e.C):
-        raise ValueError("neighbour index out of range")
-    if validate and transform == SQRT and e.dtype == torch.float64 and e.C:
-        check_f64_sqrt_domain(e)
-    if out is None:
-        out = torch.empty((C_out, nrndm), dtype=e.dtype, device=e.t.device)
-    n_sched = C_out
-    if order is not None:
-        order = order.to(device=e.t.device, dtype=torch.int32).contiguous()
-        n_sched = int(order.numel())          # a schedule over a subset of the cells: the other rows of `out` stay as they are
-        assert n_sched <= C_out
-        if n_sched == 0:
-            return out
-    ix, perm, user_out = _sorted_rows(ix, out, presorted)
-    _lib.check(_lib.lib().vcy_coldeltacor_partial(e.t.data_ptr(), d.t.data_ptr(), ix.data_ptr(), (out if perm is None else perm[1]).data_ptr(), _p(order),
-                                                  e.C, e.G, e.ld, cell0, n_sched, d_row0, nrndm, transform, rules, float(psc),
-                                                  e.code, _stream()), "coldeltacor_partial")
-    return out if perm is None else user_out.scatter_(1, perm[0], perm[1])
+
+    def launch(ix, o, order, n_sched):
+        return _lib.lib().vcy_coldeltacor_partial(e.t.data_ptr(), d.t.data_ptr(), ix.data_ptr(), o[0].data_ptr(), _p(order), e.C, e.G, e.ld,
+                                                  cell0, n_sched, d_row0, ix.shape[1], transform, rules, float(psc), e.code, _stream())
+    return _partial_launch("coldeltacor_partial", launch, e, d.C, d_row0, ixs, transform, cell0, order, (out,), validate, presorted)[0]
 
 
 def coldeltacor_partial_fused(Sx: CellMatrix, Ux: CellMatrix, gamma: torch.Tensor, q: Optional[torch.Tensor], ixs, transform: int,
                               rules: int = RULES_PARTIAL, psc: float = 0.0, dt_shift: float = 1.0, used_dt: float = 1.0, cell0: int = 0,
                               u_row0: int = 0, order: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                              validate: bool = True) -> torch.Tensor:
+                              validate: bool = True, presorted: Optional[bool] = None) -> torch.Tensor:
     """Stage C + D in one launch: correlations against the dmat the velocity chain would produce (vcy_coldeltacor_partial_fused)."""
     assert Sx.ld == Ux.ld and Sx.dtype == Ux.dtype and Sx.G == Ux.G
-    dev = Sx.t.device
-    ix = _as_i32(ixs, dev)
-    C_out, nrndm = ix.shape
-    assert u_row0 <= cell0 and cell0 + C_out <= u_row0 + Ux.C
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= Sx.C):
-        raise ValueError("neighbour index out of range")
-    if validate and transform == SQRT and Sx.dtype == torch.float64 and Sx.C:
-        check_f64_sqrt_domain(Sx)
-    if out is None:
-        out = torch.empty((C_out, nrndm), dtype=Sx.dtype, device=dev)
-    gamma = gamma.to(device=dev, dtype=torch.float32).contiguous()
-    q = None if q is None else q.to(device=dev, dtype=torch.float32).contiguous()
-    n_sched = C_out
-    if order is not None:
-        # the schedule may name only SOME of the C_out cells (e.g. the cells whose neighbours are all rank-local, while the
-        # halo exchange is still in flight): rows of ixs / out are addressed by cell id, the others are left untouched
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
-        n_sched = int(order.numel())
-        assert n_sched <= C_out
-        if n_sched == 0:
-            return out
-    ix, perm, user_out = _sorted_rows(ix, out)
-    _lib.check(_lib.lib().vcy_coldeltacor_partial_fused(Sx.t.data_ptr(), Ux.t.data_ptr(), gamma.data_ptr(), _p(q), ix.data_ptr(),
-                                                        (out if perm is None else perm[1]).data_ptr(),
-                                                        _p(order), Sx.C, Sx.G, Sx.ld, cell0, n_sched, u_row0, nrndm, transform, rules, float(psc),
-                                                        float(dt_shift), float(used_dt), Sx.code, _stream()), "coldeltacor_partial_fused")
-    return out if perm is None else user_out.scatter_(1, perm[0], perm[1])
+    gamma = gamma.to(device=Sx.t.device, dtype=torch.float32).contiguous()
+    q = None if q is None else q.to(device=Sx.t.device, dtype=torch.float32).contiguous()
 
-
-def _sched(order, dev, C_out):
-    """(order tensor or None, number of scheduled cells)."""
-    if order is None:
-        return None, C_out
-    order = order.to(device=dev, dtype=torch.int32).contiguous()
-    assert int(order.numel()) <= C_out
-    return order, int(order.numel())
+    def launch(ix, o, order, n_sched):
+        return _lib.lib().vcy_coldeltacor_partial_fused(Sx.t.data_ptr(), Ux.t.data_ptr(), gamma.data_ptr(), _p(q), ix.data_ptr(), o[0].data_ptr(),
+                                                        _p(order), Sx.C, Sx.G, Sx.ld, cell0, n_sched, u_row0, ix.shape[1], transform, rules,
+                                                        float(psc), float(dt_shift), float(used_dt), Sx.code, _stream())
+    return _partial_launch("coldeltacor_partial_fused", launch, Sx, Ux.C, u_row0, ixs, transform, cell0, order, (out,), validate, presorted)[0]
 
 
 def coldeltacor_partial_dual(e: CellMatrix, d: CellMatrix, d_rndm: CellMatrix, ixs, transform: int, rules: int = RULES_PARTIAL,
@@ -721,61 +724,31 @@ def coldeltacor_partial_dual(e: CellMatrix, d: CellMatrix, d_rndm: CellMatrix, i
     """(corr, corr_rndm): the real and the randomised-control correlations of a neighbour list in one pass
     (vcy_coldeltacor_partial_dual; analysis.py:1539-1542, 1578-1601)."""
     assert e.ld == d.ld == d_rndm.ld and e.dtype == d.dtype == d_rndm.dtype and e.G == d.G == d_rndm.G and d.C == d_rndm.C
-    ix = _as_i32(ixs, e.t.device)
-    C_out, nrndm = ix.shape
-    assert d_row0 <= cell0 and cell0 + C_out <= d_row0 + d.C
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= e.C):
-        raise ValueError("neighbour index out of range")
-    if validate and transform == SQRT and e.dtype == torch.float64 and e.C:
-        check_f64_sqrt_domain(e)
-    out = torch.empty((C_out, nrndm), dtype=e.dtype, device=e.t.device) if out is None else out
-    out_rndm = torch.empty((C_out, nrndm), dtype=e.dtype, device=e.t.device) if out_rndm is None else out_rndm
-    order, n_sched = _sched(order, e.t.device, C_out)
-    if n_sched == 0:
-        return out, out_rndm
-    ix, perm, _ = _sorted_rows(ix, out, presorted)
-    perm2 = None if perm is None else out_rndm.gather(1, perm[0])
-    _lib.check(_lib.lib().vcy_coldeltacor_partial_dual(e.t.data_ptr(), d.t.data_ptr(), d_rndm.t.data_ptr(), ix.data_ptr(),
-                                                       (out if perm is None else perm[1]).data_ptr(), (out_rndm if perm is None else perm2).data_ptr(),
-                                                       _p(order), e.C, e.G, e.ld, cell0, n_sched, d_row0, nrndm, transform, rules, float(psc),
-                                                       e.code, _stream()), "coldeltacor_partial_dual")
-    if perm is not None:
-        out.scatter_(1, perm[0], perm[1])
-        out_rndm.scatter_(1, perm[0], perm2)
-    return out, out_rndm
+
+    def launch(ix, o, order, n_sched):
+        return _lib.lib().vcy_coldeltacor_partial_dual(e.t.data_ptr(), d.t.data_ptr(), d_rndm.t.data_ptr(), ix.data_ptr(), o[0].data_ptr(),
+                                                       o[1].data_ptr(), _p(order), e.C, e.G, e.ld, cell0, n_sched, d_row0, ix.shape[1],
+                                                       transform, rules, float(psc), e.code, _stream())
+    return _partial_launch("coldeltacor_partial_dual", launch, e, d.C, d_row0, ixs, transform, cell0, order, (out, out_rndm), validate, presorted)
 
 
 def coldeltacor_partial_fused_dual(Sx: CellMatrix, Ux: CellMatrix, gamma: torch.Tensor, q: Optional[torch.Tensor], d_rndm: CellMatrix, ixs,
                                    transform: int, rules: int = RULES_PARTIAL, psc: float = 0.0, dt_shift: float = 1.0, used_dt: float = 1.0,
                                    cell0: int = 0, u_row0: int = 0, order: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                                   out_rndm: Optional[torch.Tensor] = None, validate: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+                                   out_rndm: Optional[torch.Tensor] = None, validate: bool = True,
+                                   presorted: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stage C + D + the randomised control in one launch (vcy_coldeltacor_partial_fused_dual)."""
     assert Sx.ld == Ux.ld == d_rndm.ld and Sx.dtype == Ux.dtype == d_rndm.dtype and Sx.G == Ux.G == d_rndm.G and Ux.C == d_rndm.C
-    dev = Sx.t.device
-    ix = _as_i32(ixs, dev)
-    C_out, nrndm = ix.shape
-    assert u_row0 <= cell0 and cell0 + C_out <= u_row0 + Ux.C
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= Sx.C):
-        raise ValueError("neighbour index out of range")
-    if validate and transform == SQRT and Sx.dtype == torch.float64 and Sx.C:
-        check_f64_sqrt_domain(Sx)
-    out = torch.empty((C_out, nrndm), dtype=Sx.dtype, device=dev) if out is None else out
-    out_rndm = torch.empty((C_out, nrndm), dtype=Sx.dtype, device=dev) if out_rndm is None else out_rndm
-    gamma = gamma.to(device=dev, dtype=torch.float32).contiguous()
-    q = None if q is None else q.to(device=dev, dtype=torch.float32).contiguous()
-    order, n_sched = _sched(order, dev, C_out)
-    if n_sched == 0:
-        return out, out_rndm
-    ix, perm, _ = _sorted_rows(ix, out)
-    perm2 = None if perm is None else out_rndm.gather(1, perm[0])
-    _lib.check(_lib.lib().vcy_coldeltacor_partial_fused_dual(Sx.t.data_ptr(), Ux.t.data_ptr(), gamma.data_ptr(), _p(q), d_rndm.t.data_ptr(), ix.data_ptr(),
-                                                             (out if perm is None else perm[1]).data_ptr(), (out_rndm if perm is None else perm2).data_ptr(),
-                                                             _p(order), Sx.C, Sx.G, Sx.ld, cell0, n_sched, u_row0, nrndm, transform, rules, float(psc),
-                                                             float(dt_shift), float(used_dt), Sx.code, _stream()), "coldeltacor_partial_fused_dual")
-    if perm is not None:
-        out.scatter_(1, perm[0], perm[1])
-        out_rndm.scatter_(1, perm[0], perm2)
-    return out, out_rndm
+    gamma = gamma.to(device=Sx.t.device, dtype=torch.float32).contiguous()
+    q = None if q is None else q.to(device=Sx.t.device, dtype=torch.float32).contiguous()
+
+    def launch(ix, o, order, n_sched):
+        return _lib.lib().vcy_coldeltacor_partial_fused_dual(Sx.t.data_ptr(), Ux.t.data_ptr(), gamma.data_ptr(), _p(q), d_rndm.t.data_ptr(),
+                                                             ix.data_ptr(), o[0].data_ptr(), o[1].data_ptr(), _p(order), Sx.C, Sx.G, Sx.ld, cell0,
+                                                             n_sched, u_row0, ix.shape[1], transform, rules, float(psc), float(dt_shift),
+                                                             float(used_dt), Sx.code, _stream())
+    return _partial_launch("coldeltacor_partial_fused_dual", launch, Sx, Ux.C, u_row0, ixs, transform, cell0, order, (out, out_rndm), validate,
+                           presorted)
 
 
 def coldeltacor_full(e: CellMatrix, d: CellMatrix, transform: int, psc: float = 0.0, cell0: int = 0,
@@ -841,17 +814,9 @@ def knn_pool(data: CellMatrix, indptr, indices, weights, maximum: bool = False, 
     """out[c,:] = sum_p w[p] data[indices[p],:] over CSR row c (neighbors.py:416-423 on device)."""
     dev = data.t.device
     C_out = data.C - cell0 if C_out is None else C_out
-    ip = (indptr if isinstance(indptr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(indptr).astype(np.int64))).to(device=dev, dtype=torch.int64).contiguous()
-    ix = _as_i32(indices, dev)
-    w = (weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))).to(device=dev, dtype=data.dtype).contiguous()
-    assert ip.numel() == C_out + 1 and ix.numel() == w.numel()
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= data.C):
-        raise ValueError("neighbour index out of range")
+    ip, ix, (w,), order = _pool_args(dev, data.dtype, data.C, C_out, indptr, indices, (weights,), order, validate)
     if out is None:
         out = CellMatrix.empty(C_out, data.G, data.dtype)
-    if order is not None:
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
-        assert order.numel() == C_out
     _lib.check(_lib.lib().vcy_knn_pool(data.t.data_ptr(), out.t.data_ptr(), ip.data_ptr(), ix.data_ptr(), w.data_ptr(), _p(order), data.C,
                                        data.G, data.ld, cell0, C_out, int(maximum), int(slab_genes), data.code, _stream()), "knn_pool")
     return out
@@ -863,17 +828,8 @@ def knn_pool_w2(data: CellMatrix, indptr, indices, weights, weights2, cell0: int
     out[c,:] = sum_p w[p] data[indices[p],:],  out2[c,:] = sum_p w2[p] data[indices[p],:]."""
     dev = data.t.device
     C_out = data.C - cell0 if C_out is None else C_out
-    ip = (indptr if isinstance(indptr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(indptr).astype(np.int64))).to(device=dev, dtype=torch.int64).contiguous()
-    ix = _as_i32(indices, dev)
-    as_w = lambda t: (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))).to(device=dev, dtype=data.dtype).contiguous()
-    w, w2 = as_w(weights), as_w(weights2)
-    assert ip.numel() == C_out + 1 and ix.numel() == w.numel() == w2.numel()
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= data.C):
-        raise ValueError("neighbour index out of range")
+    ip, ix, (w, w2), order = _pool_args(dev, data.dtype, data.C, C_out, indptr, indices, (weights, weights2), order, validate)
     out, out2 = CellMatrix.empty(C_out, data.G, data.dtype), CellMatrix.empty(C_out, data.G, data.dtype)
-    if order is not None:
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
-        assert order.numel() == C_out
     _lib.check(_lib.lib().vcy_knn_pool_w2(data.t.data_ptr(), out.t.data_ptr(), out2.t.data_ptr(), ip.data_ptr(), ix.data_ptr(), w.data_ptr(),
                                           w2.data_ptr(), _p(order), data.C, data.G, data.ld, cell0, C_out, int(slab_genes), data.code, _stream()),
                "knn_pool_w2")
@@ -887,17 +843,9 @@ def knn_pool2(data: CellMatrix, data2: CellMatrix, indptr, indices, weights, max
     dev = data.t.device
     assert data.t.shape == data2.t.shape and data.dtype == data2.dtype and data.G == data2.G
     C_out = data.C - cell0 if C_out is None else C_out
-    ip = (indptr if isinstance(indptr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(indptr).astype(np.int64))).to(device=dev, dtype=torch.int64).contiguous()
-    ix = _as_i32(indices, dev)
-    w = (weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))).to(device=dev, dtype=data.dtype).contiguous()
-    assert ip.numel() == C_out + 1 and ix.numel() == w.numel()
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= data.C):
-        raise ValueError("neighbour index out of range")
+    ip, ix, (w,), order = _pool_args(dev, data.dtype, data.C, C_out, indptr, indices, (weights,), order, validate)
     out = CellMatrix.empty(C_out, data.G, data.dtype) if out is None else out
     out2 = CellMatrix.empty(C_out, data.G, data.dtype) if out2 is None else out2
-    if order is not None:
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
-        assert order.numel() == C_out
     _lib.check(_lib.lib().vcy_knn_pool2(data.t.data_ptr(), out.t.data_ptr(), data2.t.data_ptr(), out2.t.data_ptr(), ip.data_ptr(), ix.data_ptr(),
                                         w.data_ptr(), _p(order), data.C, data.G, data.ld, cell0, C_out, int(maximum), int(slab_genes), data.code,
                                         _stream()), "knn_pool2")
@@ -913,28 +861,18 @@ def knn_pool_counts(cS: CountMatrix, cU: Optional[CountMatrix], scaleS, scaleU, 
     dev = cS.t.device
     dt = resolve_dtype(dtype)
     C_out = cS.C - cell0 if C_out is None else C_out
-    ip = (indptr if isinstance(indptr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(indptr).astype(np.int64))).to(device=dev, dtype=torch.int64).contiguous()
-    ix = _as_i32(indices, dev)
-    w = (weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))).to(device=dev, dtype=dt).contiguous()
-    f64 = lambda t: None if t is None else (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()
-    sS = f64(scaleS) if scaleS is not None else torch.ones(cS.C, dtype=torch.float64, device=dev)
-    sU = None
+    ip, ix, (w,), order = _pool_args(dev, dt, cS.C, C_out, indptr, indices, (weights,), order, validate)
+    sS, sU = _scale_vec(scaleS, cS.C, dev), None
     if cU is not None:
         assert cU.G == cS.G
         if cU.t.dtype != cS.t.dtype:          # one launch pools both layers: bring them to the wider storage
             widen = lambda m: m if m.t.dtype == torch.int16 else CountMatrix(m.t.to(torch.int16), m.G)
             cS, cU = widen(cS), widen(cU)
         assert cU.t.shape == cS.t.shape
-        sU = f64(scaleU) if scaleU is not None else torch.ones(cS.C, dtype=torch.float64, device=dev)
-    assert ip.numel() == C_out + 1 and ix.numel() == w.numel() and sS.numel() == cS.C
-    if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= cS.C):
-        raise ValueError("neighbour index out of range")
+        sU = _scale_vec(scaleU, cS.C, dev)
     out = CellMatrix.empty(C_out, cS.G, dt) if out is None else out
     if cU is not None:
         out2 = CellMatrix.empty(C_out, cS.G, dt) if out2 is None else out2
-    if order is not None:
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
-        assert order.numel() == C_out
     _lib.check(_lib.lib().vcy_knn_pool_counts(cS.t.data_ptr(), None if cU is None else cU.t.data_ptr(), sS.data_ptr(), _p(sU), out.t.data_ptr(),
                                               None if cU is None else out2.t.data_ptr(), ip.data_ptr(), ix.data_ptr(), w.data_ptr(), _p(order),
                                               cS.C, cS.G, cS.ld, out.ld, cell0, C_out, int(maximum), int(slab_genes), cS.code, out.code, _stream()),
@@ -1798,7 +1736,7 @@ def embedding_scaling(hi: CellMatrix, dS: CellMatrix, ixs, wdiff: torch.Tensor, 
         w2 = wdiff_rndm.to(device=dev, dtype=hi.dtype).contiguous()
     cos = torch.empty(C_out, dtype=torch.float64, device=dev)
     cos2 = torch.empty(C_out, dtype=torch.float64, device=dev) if dual else None
-    order, n_sched = _sched(order, dev, C_out)
+    order, n_sched = _schedule(order, dev, C_out)
     assert n_sched == C_out, "embedding_scaling: the schedule must cover every cell"
     _lib.check(L.vcy_embedding_scaling(hi.t.data_ptr(), dS.t.data_ptr(), None if not dual else dS_rndm.t.data_ptr(), ix.data_ptr(), w.data_ptr(),
                                        _p(w2), _p(order), cos.data_ptr(), _p(cos2), hi.C, hi.G, hi.ld, C_out, n, hi.code, _stream()), "embedding_scaling")

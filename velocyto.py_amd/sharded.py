@@ -33,7 +33,7 @@ import torch
 
 from . import distributed as D
 from . import ops
-from .analysis import VelocytoLoom, markov_csr
+from .analysis import VelocytoLoom, embedding_shift, fix_correlations, markov_csr, sampling_plan, stage_d_args
 from .ops import CellMatrix
 
 _MATRICES = ("S", "U", "S_sz", "U_sz", "S_norm", "U_norm", "Sx", "Ux", "Sx_sz", "Ux_sz", "Upred", "velocity", "delta_S", "delta_S_rndm",
@@ -216,31 +216,18 @@ class ShardedLoom:
         indptr = torch.arange(0, (self.nloc + 1) * (k + 1), k + 1, device=self.dev, dtype=torch.int64)
         w = vals.reshape(-1).to(self._dtype).contiguous()
         order = ops.hilbert_order(space_run[self.c0:self.c1, :2].contiguous()) if space_run.shape[1] >= 2 else None
-        n_all = self.nloc + plan.n_recv
         if self._counts is not None and "S_sz" in self._sz_scale and "U_sz" in self._sz_scale:
             bufs, scales = [], []
             for n in ("S", "U"):
                 cm = self._counts[n]
-                buf = torch.zeros((n_all, cm.ld), dtype=cm.t.dtype, device=self.dev)
-                buf[:self.nloc] = cm.t
-                if plan.n_recv:
-                    v = buf.view(torch.int32)                            # 16-bit rows travel as 32-bit words (ld is a multiple of 64)
-                    plan.end(plan.begin(v[:self.nloc], recv_out=v[self.nloc:]), v, row0=self.nloc)
-                bufs.append(ops.CountMatrix(buf, cm.G))
+                bufs.append(ops.CountMatrix(plan.compact(cm.t), cm.G))
                 sc = self._sz_scale[n + "_sz"]
                 scales.append(torch.cat([sc, plan.fetch(sc[:, None]).reshape(-1)]) if plan.n_recv else sc)
             Sx, Ux = ops.knn_pool_counts(bufs[0], bufs[1], scales[0], scales[1], indptr, local_cols, w, dtype=self._dtype, maximum=maximum,
                                          C_out=self.nloc, order=order, validate=False)
             halo_bytes = 2 * plan.n_recv * self._counts["S"].ld * 2
         else:
-            mats = []
-            for n in ("S_sz", "U_sz"):
-                m = self._m[n]
-                buf = CellMatrix(torch.zeros((n_all, m.ld), dtype=m.dtype, device=self.dev), m.G)
-                buf.t[:self.nloc] = m.t
-                if plan.n_recv:
-                    plan.end(plan.begin(m.t, recv_out=buf.t[self.nloc:]), buf.t, row0=self.nloc)
-                mats.append(buf)
+            mats = [CellMatrix(plan.compact(self._m[n].t), self._m[n].G) for n in ("S_sz", "U_sz")]
             Sx, Ux = ops.knn_pool2(mats[0], mats[1], indptr, local_cols, w, maximum=maximum, C_out=self.nloc, order=order, validate=False)
             halo_bytes = 2 * plan.n_recv * self._m["S_sz"].ld * self._m["S_sz"].t.element_size()
         self.exchange_bytes["halo_pool"] = halo_bytes
@@ -343,33 +330,16 @@ class ShardedLoom:
         if not knn_random or transform == "logratio" or "pcs" in hidim or hidim != "Sx_sz":
             raise NotImplementedError("ShardedLoom.estimate_transition_prob covers hidim='Sx_sz', knn_random=True and the "
                                       "linear / sqrt / log transforms")
-        if transform not in ("log", "linear", "sqrt"):
-            raise NotImplementedError(f"transform={transform} is not a valid parameter")
-        if ndims is not None:
-            raise ValueError(f"ndims was set to {ndims} but hidim != 'pcs'. Set ndims = None for hidim='{hidim}'")
         C = self.C
-        if n_sight is None and n_neighbors is None:
-            n_neighbors = int(C / 5)
-        if (n_sight is not None) and (n_neighbors is not None) and n_neighbors != n_sight:
-            raise ValueError("n_sight and n_neighbors are different names for the same parameter, they cannot be set differently")
-        if n_sight is not None and n_neighbors is None:
-            n_neighbors = n_sight
-        if psc is None:
-            psc = 1.0 if transform == "log" else (1e-10 if transform == "sqrt" else 0)
+        n_neighbors, psc, mode, kern = stage_d_args(C, transform, hidim, ndims, n_sight, n_neighbors, psc)
         np.random.seed(random_seed)                                                  # :1529
         self.which_hidim = hidim
         hi, dS = self._m[hidim], self._m["delta_S"]
         embedding = np.asarray(getattr(self, embed), dtype=np.float64)
         self.embedding = embedding
-        mode = {"linear": 0, "sqrt": 1, "log": 2}[transform]
-        kern = {"linear": ops.LINEAR, "sqrt": ops.SQRT, "log": ops.LOG10}[transform]
         if kern == ops.SQRT and hi.dtype == torch.float64:
-            # judged on the whole matrix, by every rank alike (a rank raising alone would leave the others in the next collective)
-            m = hi.t.abs().max().double().reshape(1) if hi.C else torch.zeros(1, dtype=torch.float64, device=self.dev)
-            D.all_reduce_max(m, self._group)
-            if float(m) >= ops.F64_SQRT_MAX:
-                raise ValueError(f"colDeltaCor sqrt transform in f64: |e| reaches {float(m):.3g}, outside the supported range "
-                                 f"(< {ops.F64_SQRT_MAX:g})")
+            # judged on the whole matrix, by every rank alike
+            D.check_f64_sqrt_domain(hi.t.abs().max() if hi.C else torch.zeros(1, dtype=torch.float64, device=self.dev), self._group)
         stats = D.all_reduce_abs_stats(ops.abs_stats(hi), self._group)
         rules = ops.partial_rules_for(hi, kern, psc, stats=stats, cells=C, literal=bool(getattr(self, "literal_rule", False)),
                                       domain_checked=True)
@@ -392,9 +362,7 @@ class ShardedLoom:
         knn_ix, _ = ops.knn_search(emb_run, n_neighbors + 1, include_self=False, q0=self.c0, Q=self.nloc)
         knn_user = self._user[knn_ix.long()]
         n_cand = int(knn_ix.shape[1])
-        p = np.linspace(sampling_probs[0], sampling_probs[1], n_cand)
-        p = p / p.sum()
-        size = int(sampled_fraction * (n_neighbors + 1))
+        p, size = sampling_plan(sampling_probs, n_cand, sampled_fraction, n_neighbors)
         # the facade's numpy stream, replayed whole on every rank (same RNG state afterwards everywhere); the rank keeps its rows
         t_rep = time.perf_counter()
         sampling_ixs = ops.choice_stream_host(n_cand, size, p, C)
@@ -411,10 +379,7 @@ class ShardedLoom:
         need[self.c0:self.c1] = True
         plan = D.HaloPlan(need, C, self._group)
         self._d_plan = plan
-        e = CellMatrix(torch.zeros((self.nloc + plan.n_recv, hi.ld), dtype=hi.dtype, device=self.dev), hi.G)
-        e.t[:self.nloc] = hi.t
-        if plan.n_recv:
-            plan.end(plan.begin(hi.t, recv_out=e.t[self.nloc:]), e.t, row0=self.nloc)
+        e = CellMatrix(plan.compact(hi.t), hi.G)
         self.exchange_bytes["halo_stage_d"] = plan.n_recv * hi.ld * hi.t.element_size()
         self._e = e
         nk = plan.localize(neigh_run)
@@ -429,14 +394,8 @@ class ShardedLoom:
             else:
                 ops.coldeltacor_partial(e, dmat, nk, kern, rules, psc, cell0=0, order=order, out=corr, validate=False)
         self.corr_calc = "knn_random"
-        if ops.corr_fixup(corr, nk, zero_self=True, fix_nan=True, nan_to=1.0):                      # :1604-1607
-            logging.warning("Nans encountered in corrcoef and corrected to 1s. If not identical cells were present it is probably a small isolated cluster converging after imputation.")
-        self._corr = corr
-        self._corr_random = None
-        if calculate_randomized:
-            if ops.corr_fixup(corr_r, nk, zero_self=True, fix_nan=True, nan_to=1.0):
-                logging.warning("Nans encountered in corrcoef_random and corrected to 1s. If not identical cells were present it is probably a small isolated cluster converging after imputation.")
-            self._corr_random = corr_r
+        fix_correlations(corr, corr_r, nk)                                                         # :1604-1607
+        self._corr, self._corr_random = corr, corr_r
         self._timed("estimate_transition_prob", t0)
 
     # ------------------------------------------------------------------ stage E
@@ -444,35 +403,18 @@ class ShardedLoom:
         """analysis.py:1670-1733 in neighbour-list form, rank-local: the transition probabilities of the rank's rows, the expression
         scaling from the rows of hi the stage-D halo already holds."""
         t0 = time.perf_counter()
-        nrun = self._neigh_run
-        names = [("_corr", "delta_S")] + ([("_corr_random", "delta_S_rndm")] if self._corr_random is not None else [])
-        parts = [ops.transition_prob(getattr(self, cn).contiguous(), nrun, self._emb_run, sigma_corr, cell0=self.c0) for cn, _ in names]
-        scalings = [None] * len(names)
-        if expression_scaling:
-            e, nk, n_all = self._e, self._neigh_k, self._e.C
-            n = int(nk.shape[1])
+        e = self._e
 
-            def padded(m):                                           # own rows at the top of an e-sized buffer (the kernel's shape)
-                if m.C == n_all:
-                    return m
-                out = CellMatrix(torch.zeros_like(e.t), e.G)
-                out.t[:m.C] = m.t
-                return out
-            dS_r = padded(self._m[names[1][1]]) if len(names) == 2 else None
-            cos = None
-            if self.nloc:
-                cos = ops.embedding_scaling(e, padded(self._m["delta_S"]), nk, parts[0][1], dS_r, parts[1][1] if len(names) == 2 else None,
-                                            validate=False)
-            if cos is None:
-                indptr = torch.arange(0, (self.nloc + 1) * n, n, dtype=torch.int64, device=self.dev)
-                if len(names) == 2:
-                    estims = ops.knn_pool_w2(e, indptr, nk.reshape(-1), parts[0][1].reshape(-1), parts[1][1].reshape(-1), C_out=self.nloc, validate=False)
-                else:
-                    estims = (ops.knn_pool(e, indptr, nk.reshape(-1), parts[0][1].reshape(-1), C_out=self.nloc, validate=False),)
-                cos = [ops.row_cosproj(self._m[dn], estims[i]) for i, (_, dn) in enumerate(names)]
-            for i in range(len(names)):
-                scalings[i] = torch.clamp(cos[i] / scaling_penalty, 0, 1)
-        res = [(tp, de if sc is None else de * sc[:, None], sc) for (tp, _, de), sc in zip(parts, scalings)]
+        def padded(m):                                               # own rows at the top of an e-sized buffer (the kernel's shape)
+            if m.C == e.C:
+                return m
+            out = CellMatrix(torch.zeros_like(e.t), e.G)
+            out.t[:m.C] = m.t
+            return out
+        dS = padded(self._m["delta_S"]) if expression_scaling else None
+        dS_r = padded(self._m["delta_S_rndm"]) if expression_scaling and self._corr_random is not None else None
+        res = embedding_shift(e, dS, dS_r, self._neigh_k, self._neigh_run, self._corr, self._corr_random, self._emb_run, sigma_corr,
+                              expression_scaling, scaling_penalty, cell0=self.c0)
         self._tp, self._delta_embedding, self._scaling = res[0]
         self._tp_random = self._delta_embedding_random = self._scaling_rndm = None
         if len(res) == 2:
