@@ -482,6 +482,134 @@ def box_wls2_moments(sw, sx, sy, sxx, sxy, lo_m, hi_m, lo_q, hi_q) -> Tuple[floa
     return float(m), float(q)
 
 
+# An independent statement of the same problem, for the tests of the fit kernels: long double, data centred on the weighted means
+# (no sxx * sw - sx^2), the active set found by enumeration.  box_wls2 above shares its formula and its candidate order with
+# csrc/fit.hip, so a mistake ported to both agrees with itself; this one shares neither.
+FIT_REGIONS = tuple(f"m_{a}/q_{b}" for a in ("in", "lo", "hi") for b in ("in", "lo", "hi"))
+
+
+def fit_box_reference(x, y, w, lo_m, hi_m, lo_q, hi_q) -> Tuple[float, float, str]:
+    """argmin of sum w (x m + q - y)^2 over [lo_m, hi_m] x [lo_q, hi_q] -> (m, q, region).  The nine candidates (interior point,
+    the free minimum of each edge, the corners) are evaluated from the centred data, sum w (m xc + (m xbar + q - ybar) - yc)^2,
+    and the feasible one with the least objective wins (earlier in the order interior, edges, corners on an exact tie).
+    region is one of FIT_REGIONS, or "degenerate" when the weighted x has no spread or sum w == 0: the minimiser is then a line
+    (or everything), the (m, q) returned is one feasible point of it."""
+    L = np.longdouble
+    x, y, w = (np.asarray(a, dtype=L).ravel() for a in (x, y, w))
+    lo_m, hi_m, lo_q, hi_q = L(lo_m), L(hi_m), L(lo_q), L(hi_q)
+    sw = w.sum()
+    on = w != 0
+    if not (sw > 0) or not on.any():
+        return float(lo_m), float(lo_q) if np.isfinite(lo_q) else 0.0, "degenerate"
+    xbar, ybar = (w * x).sum() / sw, (w * y).sum() / sw
+    xc, yc = x - xbar, y - ybar
+    spread = x[on].max() > x[on].min()
+    sxx_c, sxy_c = (w * xc * xc).sum(), (w * xc * yc).sum()
+    sxx_raw = sxx_c + sw * xbar * xbar                     # sums of non-negative terms: nothing cancels
+
+    def f(m, q):
+        with np.errstate(invalid="ignore", over="ignore"):  # an infinite bound (no box) gives inf - inf in its corners: never the least
+            r = m * xc + (m * xbar + q - ybar) - yc
+            return (w * r * r).sum()
+
+    cands = []                                             # (region, m, q)
+    if spread:
+        m = sxy_c / sxx_c
+        cands.append(("m_in/q_in", m, ybar - m * xbar))
+    for tag, q in (("lo", lo_q), ("hi", hi_q)):            # q on a bound, m free
+        if sxx_raw > 0:
+            cands.append((f"m_in/q_{tag}", (sxy_c + sw * xbar * (ybar - q)) / sxx_raw, q))
+    for tag, m in (("lo", lo_m), ("hi", hi_m)):            # m on a bound, q free
+        cands.append((f"m_{tag}/q_in", m, ybar - m * xbar))
+    for tm, m in (("lo", lo_m), ("hi", hi_m)):
+        for tq, q in (("lo", lo_q), ("hi", hi_q)):
+            cands.append((f"m_{tm}/q_{tq}", m, q))
+    best = None
+    for region, m, q in cands:
+        if not (lo_m <= m <= hi_m and lo_q <= q <= hi_q):
+            continue
+        v = f(m, q)
+        if best is None or v < best[0]:
+            best = (v, m, q, region)
+    _, m, q, region = best
+    return float(m), float(q), (region if spread else "degenerate")
+
+
+def fit_objective(x, y, w, m, q) -> float:
+    """sum w (x m + q - y)^2 from the raw data in long double."""
+    L = np.longdouble
+    x, y, w = (np.asarray(a, dtype=L).ravel() for a in (x, y, w))
+    r = L(m) * x + L(q) - y
+    return float((w * r * r).sum())
+
+
+def fit_kkt(x, y, w, m, q, lo_m, hi_m, lo_q, hi_q) -> float:
+    """Scaled violation of the first-order optimality conditions of the box problem at any (m, q): the gradient
+    (2 sum w r x, 2 sum w r), r = m x + q - y, from the raw data in long double; a free variable wants |g| = 0, one on its lower
+    bound g >= 0, one on its upper bound g <= 0 (a variable whose bounds coincide wants nothing).  Each violation is divided by
+    2 sum w |x| (|m x| + |q| + |y|) for m and by the same sum without |x| for q; the larger of the two is returned (inf outside
+    the box)."""
+    L = np.longdouble
+    x, y, w = (np.asarray(a, dtype=L).ravel() for a in (x, y, w))
+    m, q, lo_m, hi_m, lo_q, hi_q = (L(v) for v in (m, q, lo_m, hi_m, lo_q, hi_q))
+    r = m * x + q - y
+    mag = np.abs(m * x) + np.abs(q) + np.abs(y)
+    out = L(0)
+    for g, scale, v, lo, hi in ((2 * (w * r * x).sum(), 2 * (w * np.abs(x) * mag).sum(), m, lo_m, hi_m),
+                                (2 * (w * r).sum(), 2 * (w * mag).sum(), q, lo_q, hi_q)):
+        if not (lo <= v <= hi):
+            return float("inf")
+        if lo == hi:
+            viol = L(0)
+        elif v == lo:
+            viol = max(L(0), -g)
+        elif v == hi:
+            viol = max(L(0), g)
+        else:
+            viol = abs(g)
+        if viol > 0:
+            out = max(out, viol / scale)
+    return float(out)
+
+
+def r2_reference(m, q, x, y) -> float:
+    """The unweighted coefficient of determination of estimation.py:323-331 in long double, centred (sum (ybar - y)^2 as the
+    reference writes it, residuals from the data), -1e16 when it is not finite."""
+    L = np.longdouble
+    x, y = np.asarray(x, dtype=L).ravel(), np.asarray(y, dtype=L).ravel()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = L(m) * x + L(q) - y
+        d = y.mean() - y
+        r2 = 1 - (r * r).sum() / (d * d).sum()
+    return float(r2) if np.isfinite(r2) else -1e16
+
+
+def r2_expansion(m, q, x, y) -> float:
+    """R2 the way csrc/fit.hip evaluates it, from the raw moments in f64: ssres = m^2 Sxx + n q^2 + Syy + 2 m q Sx - 2 m Sxy
+    - 2 q Sy, sstot = Syy - Sy^2 / n.  Kept next to r2_reference so that the cost of the expansion can be measured on the CPU."""
+    x, y = np.asarray(x, dtype=np.float64).ravel(), np.asarray(y, dtype=np.float64).ravel()
+    n = float(x.size)
+    sx, sy, sxx, sxy, syy = x.sum(), y.sum(), (x * x).sum(), (x * y).sum(), (y * y).sum()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ssres = m * m * sxx + n * q * q + syy + 2 * m * q * sx - 2 * m * sxy - 2 * q * sy
+        r2 = 1.0 - ssres / (syy - sy * sy / n)
+    return float(r2) if np.isfinite(r2) else -1e16
+
+
+def fit_condition(x, y, w) -> Tuple[float, float, float, float]:
+    """What the error bounds of the raw-moment solve are stated in: (kappa_fit, kappa_r2, scale_m, scale_q) with
+    kappa_fit = Swxx Sw / det, kappa_r2 = Syy / sstot (both from centred long-double sums: Swxx Sw / (Sw * centred Swxx)),
+    scale_m = sum w |x y| / sum w x^2 and scale_q = sum w |y| / sum w, the sizes of the quotients whose numerators cancel."""
+    L = np.longdouble
+    x, y, w = (np.asarray(a, dtype=L).ravel() for a in (x, y, w))
+    sw = w.sum()
+    xc = x - (w * x).sum() / sw
+    swxx = (w * x * x).sum()
+    yc = y - y.mean()
+    return (float(swxx / (w * xc * xc).sum()), float((y * y).sum() / (yc * yc).sum()),
+            float((w * np.abs(x * y)).sum() / swxx), float((w * np.abs(y)).sum() / sw))
+
+
 def fit_slope_weighted_offset(Y, X, W, fixperc_q=False, limit_gamma=False, exact=False):
     """estimation.fit_slope_weighted_offset + _fit1_slope_weighted_offset (estimation.py:212-241, 337-366).
     exact=False replays the reference's SciPy calls; exact=True solves the same box-constrained
