@@ -935,6 +935,166 @@ def diffuse(x, tr, n_steps=10, mode="path_integral"):
     return acc if mode == "path_integral" else v
 
 
+# --------------------------------------------------------------------------- long-double references of stage E/F and the Markov chain
+# Independent restatements in numpy long double (x87 extended: 64-bit significand), sharing no formula with the functions above:
+# what tests/test_gpu_markov_kernels.py holds the device kernels to, pinned on the f64 restatements by tests/test_markov_oracle.py.
+_LD = np.longdouble
+
+
+def transition_prob_reference(corr, ixs, emb, sigma, cell0=0):
+    """Stage E in neighbour-list form (analysis.py:1697-1712): row r of corr / ixs belongs to cell cell0 + r, ixs and emb are global.
+    The softmax is taken with the row maximum subtracted; a unit vector is 0 where ixs names the cell itself and NaN where another
+    cell has the cell's coordinates (0/0, analysis.py:1704-1708).
+    Returns tp, wdiff = tp - 1/n, delta_embedding (long double) and cond = sum_n |tp - 1/n| per cell."""
+    z = np.asarray(corr, dtype=_LD) / _LD(sigma)
+    ixs = np.asarray(ixs)
+    R, n = z.shape
+    e = np.exp(z - z.max(1, keepdims=True))
+    tp = e / e.sum(1, keepdims=True)
+    wd = tp - _LD(1) / _LD(n)
+    E = np.asarray(emb, dtype=_LD)
+    cells = cell0 + np.arange(R)
+    d = E[ixs] - E[cells][:, None, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        unit = d / np.sqrt((d * d).sum(-1))[..., None]
+    unit[ixs == cells[:, None]] = 0
+    de = (wd[..., None] * unit).sum(1)
+    return tp, wd, de, np.abs(wd).sum(1)
+
+
+def _ld_gauss(d2, sigma):
+    s2 = _LD(sigma) * _LD(sigma)
+    return np.exp(-d2 / (2 * s2)) / np.sqrt(2 * _LD(np.pi) * s2)           # (np.pi in f64: the device's own constant)
+
+
+def _ld_sqdist(E):
+    d2 = np.zeros((E.shape[0], E.shape[0]), dtype=_LD)
+    for a in range(E.shape[1]):
+        df = E[:, a][:, None] - E[:, a][None, :]
+        d2 += df * df
+    return d2
+
+
+def markov_reference(indptr, indices, pval, emb, sigma_D, sigma_W):
+    """The dense chain of analysis.py:1853-1862 in long double, from P in CSR form (one entry per stored position).
+    A row of P with no entries has maximum 0 and sum 0: it comes out NaN, as it does in the reference."""
+    indptr, indices = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    n = indptr.size - 1
+    P = np.zeros((n, n), dtype=_LD)
+    P[np.repeat(np.arange(n), np.diff(indptr)), indices] = np.asarray(pval, dtype=_LD)
+    d2 = _ld_sqdist(np.asarray(emb, dtype=_LD))
+    t = P * _ld_gauss(d2, sigma_D)
+    t[np.arange(n), np.arange(n)] = t.max(1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = t / t.sum(1, keepdims=True)
+    kw = _ld_gauss(d2, sigma_W)
+    kw = kw / kw.sum(1, keepdims=True)
+    tr = _LD(0.8) * t + _LD(0.2) * kw
+    return tr / tr.sum(1, keepdims=True)
+
+
+def markov_factors_reference(indptr, indices, pval, emb, sigma_D, sigma_W):
+    """The same chain as tr[c, j] = (0.2 K_W(c, j) / kw[c] + s[c, j]) / tot[c], in long double: s = 0.8 t (t the normalised sparse
+    part, diagonal = row maximum) in CSC form sorted by (column, row) with every diagonal stored, kw the row sums of K_W, tot the row
+    sums of 0.2 K_W / kw + s.  Returns (colptr, rowidx, scsc, tot, kw)."""
+    indptr, indices = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    n = indptr.size - 1
+    rows = np.repeat(np.arange(n), np.diff(indptr))
+    d2 = _ld_sqdist(np.asarray(emb, dtype=_LD))
+    val = np.asarray(pval, dtype=_LD) * _ld_gauss(d2[rows, indices], sigma_D)
+    mx = np.zeros(n, dtype=_LD)
+    np.maximum.at(mx, rows, val)
+    off = rows != indices
+    sm = mx.copy()
+    np.add.at(sm, rows[off], val[off])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s_off, s_diag = _LD(0.8) * val[off] / sm[rows[off]], _LD(0.8) * mx / sm
+    kwf = _ld_gauss(d2, sigma_W)
+    kw = kwf.sum(1)
+    tot = (_LD(0.2) * kwf / kw[:, None]).sum(1) + s_diag
+    np.add.at(tot, rows[off], s_off)
+    r, c, s = np.concatenate([rows[off], np.arange(n)]), np.concatenate([indices[off], np.arange(n)]), np.concatenate([s_off, s_diag])
+    order = np.argsort(c * n + r, kind="stable")
+    colptr = np.concatenate([[0], np.cumsum(np.bincount(c, minlength=n))]).astype(np.int64)
+    return colptr, r[order].astype(np.int32), s[order], tot, kw
+
+
+def markov_scaled_coords(emb, sigma_W):
+    """es = embedding * sqrt(log2(e) / (2 sigma_W^2)) in long double: exp(-d^2 / (2 sigma_W^2)) = 2^(-|es_c - es_j|^2)."""
+    return np.asarray(emb, dtype=_LD) * np.sqrt(np.log2(np.exp(_LD(1))) / (2 * _LD(sigma_W) * _LD(sigma_W)))
+
+
+def _csc_half(v, colptr, rowidx, scsc, dtype):
+    colptr = np.asarray(colptr, dtype=np.int64)
+    n = colptr.size - 1
+    col = np.repeat(np.arange(n), np.diff(colptr))
+    out = np.zeros(n, dtype=dtype)
+    np.add.at(out, col, np.asarray(scsc, dtype=dtype) * v[np.asarray(rowidx, dtype=np.int64)])
+    return out
+
+
+def gauss_step_matrices(tot, kw, es, sigma_W, targets=None):
+    """(A, W), long double (n, targets): the Gaussian half of a step is x @ A, its sensitivity S = |x| @ W (gauss_step_reference)."""
+    tot, kw = (np.asarray(a, dtype=_LD) for a in (tot, kw))
+    es = np.asarray(es, dtype=_LD)
+    et = es if targets is None else es[np.asarray(targets)]
+    d2 = np.zeros((es.shape[0], et.shape[0]), dtype=_LD)
+    l1 = np.zeros_like(d2)
+    for a in range(es.shape[1]):
+        df = es[:, a][:, None] - et[:, a][None, :]
+        d2 += df * df
+        l1 += np.abs(df)
+    A = np.exp2(-d2) * (_LD(0.2) / (tot * kw * np.sqrt(2 * _LD(np.pi) * _LD(sigma_W) * _LD(sigma_W))))[:, None]
+    return A, np.abs(A) * (1 + np.abs(es).max() * l1)
+
+
+def sparse_half_reference(x, tot, colptr, rowidx, scsc):
+    """The sparse half of a factored step in long double: (ys, T, terms), ys[j] = sum_c v[c] s[c, j], T[j] = sum_c |v[c] s[c, j]| - what
+    the f64 rounding of that half is proportional to - and the number of stored entries of column j."""
+    v = np.asarray(x, dtype=_LD) / np.asarray(tot, dtype=_LD)
+    return _csc_half(v, colptr, rowidx, scsc, _LD), _csc_half(np.abs(v), colptr, rowidx, np.abs(np.asarray(scsc, dtype=_LD)), _LD), np.diff(np.asarray(colptr, dtype=np.int64))
+
+
+def gauss_step_reference(x, tot, kw, colptr, rowidx, scsc, es, sigma_W, targets=None):
+    """One step of the factored chain from its f64 factors, in long double:
+        y[j] = sum_c v[c] s[c, j] + sum_c u[c] 2^(-|es_c - es_j|^2),   v = x / tot,  u = 0.2 v / (kw sqrt(2 pi sigma_W^2)),
+    s in CSC form, es the scaled coordinates (markov_scaled_coords, or the f64 values a caller holds); for the cells of `targets`
+    only when given.
+    Returns (y, S): S[j] = sum_c |u[c]| 2^(-d2[c, j]) (1 + M |es_c - es_j|_1), M = max |es| - the first-order bound, per unit
+    roundoff, on what rounding the coordinates (and the terms) to the compute type can do to target j."""
+    x = np.asarray(x, dtype=_LD)
+    A, W = gauss_step_matrices(tot, kw, es, sigma_W, targets)
+    ys = _csc_half(x / np.asarray(tot, dtype=_LD), colptr, rowidx, scsc, _LD)
+    return (ys if targets is None else ys[np.asarray(targets)]) + x @ A, np.abs(x) @ W
+
+
+def gauss_step_emulated(x, tot, kw, colptr, rowidx, scsc, es, sigma_W, dtype, gauss_only=False):
+    """The same step in numpy arithmetic of `dtype` the way the device orders it: coordinates and u rounded to dtype first,
+    differences, squares and exp2 in dtype, eight terms folded in dtype before they are added to an f64 accumulator; the sparse
+    half in f64 (gauss_only: left out).  Only a measuring stick: the K of the bound 4 K u S is what its Gaussian half loses against
+    gauss_step_reference's."""
+    dt = np.dtype(dtype).type
+    x, tot, kw = (np.asarray(a, dtype=np.float64) for a in (x, tot, kw))
+    v = x / tot
+    u = (0.2 / np.sqrt(2.0 * np.pi * sigma_W * sigma_W) * v / kw).astype(dt)
+    er = np.asarray(es, dtype=np.float64).astype(dt)
+    n = er.shape[0]
+    d2 = np.zeros((n, n), dtype=dt)
+    for a in range(er.shape[1]):
+        df = er[:, a][None, :] - er[:, a][:, None]                         # [c, j] = es_j - es_c
+        d2 = df * df + d2
+    term = u[:, None] * np.exp2(-d2)
+    pad = (-n) % 8
+    if pad:
+        term = np.concatenate([term, np.zeros((pad, n), dtype=dt)])
+    term = term.reshape(-1, 8, n)
+    fold = np.zeros((term.shape[0], n), dtype=dt)
+    for q in range(8):
+        fold = term[:, q, :] + fold
+    g = fold.astype(np.float64).sum(0)
+    return g if gauss_only else _csc_half(v, colptr, rowidx, scsc, np.float64) + g
+
+
 # --------------------------------------------------------------------------- "next" rows (SURVEY.md section 8f)
 def knn_query(points, queries, k) -> Tuple[np.ndarray, np.ndarray]:
     """NearestNeighbors(...).fit(points).kneighbors(queries): exact fp64 brute force, nearest first, ties by index."""

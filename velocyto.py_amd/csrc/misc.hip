@@ -189,6 +189,30 @@ __global__ void k_corr_fixup(T *__restrict__ vals, const int32_t *__restrict__ i
 //   u_n = (emb[i_n] - emb[c]) / |emb[i_n] - emb[c]|, 0 on the diagonal  (:1704-1708; 0/0 = NaN otherwise)
 //   delta_embedding[c] = sum_n p_n u_n - (1/n) sum_n u_n               (:1710-1712)
 //   wdiff[c,n] = p_n - 1/n        (weights of the expression-scaling pooling, :1716)
+// The softmax of stage E to the last few bits (tests/test_gpu_markov_kernels.py holds tp to 4 ulps of a long-double reference).
+// exp(c / sigma): q = c / sigma is half an ulp of up to 1 / sigma off, which exp() turns into |q| 2^-53 of relative error (250 ulps at
+// corr = 1, sigma_corr = 0.005).  c - q sigma is exact in one fma, and exp(q + d) = exp(q) (1 + d): the kernel carries (e, d).
+__device__ __forceinline__ double exp_quot(double c, double sigma, double &d)
+{
+    const double q = c / sigma;
+    d = fma(-q, sigma, c) / sigma;
+    return exp(q);
+}
+// (hi, lo) += (b, bl): hi + b with its rounding error (Knuth) and the partner's low part gathered in lo; symmetric in the two operands
+__device__ __forceinline__ void two_sum(double &hi, double &lo, double b, double bl)
+{
+    const double s = hi + b, bb = s - hi;
+    const double err = (hi - (s - bb)) + (b - bb);
+    hi = s;
+    lo = (lo + bl) + err;
+}
+// e (1 + d) / (zh + zl) rounded once: the quotient e / zh, its exact remainder, and the first-order terms of d and zl
+__device__ __forceinline__ double softmax_quot(double e, double d, double zh, double zl)
+{
+    const double p0 = e / zh;
+    return p0 + (fma(-p0, zh, e) + p0 * fma(d, zh, -zl)) / zh;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_transition_prob(const T *__restrict__ corr, const int32_t *__restrict__ ixs,
                                                           const double *__restrict__ emb, int edim, T *__restrict__ tp, T *__restrict__ wdiff,
@@ -200,12 +224,15 @@ __global__ __launch_bounds__(256) void k_transition_prob(const T *__restrict__ c
     const int64_t c = cell0 + cl;
     const T *crow = corr + cl * n;
     const int32_t *irow = ixs + cl * n;
-    double z = 0.0;
-    for (int k = lane; k < n; k += 64) z += exp((double)crow[k] / sigma);
-    z = wave_sum(z);
+    double z = 0.0, zl = 0.0;          // the normaliser enters every p: a (hi, lo) pair that keeps the sum's rounding errors
+    for (int k = lane; k < n; k += 64) { double d; const double e = exp_quot((double)crow[k], sigma, d); two_sum(z, zl, e, e * d); }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) two_sum(z, zl, __shfl_xor(z, off, 64), __shfl_xor(zl, off, 64));   // the same pair in every lane
     double acc[4] = {0, 0, 0, 0};   // edim <= 4
     for (int k = lane; k < n; k += 64) {
-        const double p = exp((double)crow[k] / sigma) / z;
+        double d;
+        const double e = exp_quot((double)crow[k], sigma, d);
+        const double p = softmax_quot(e, d, z, zl);
         const int i = irow[k];
         if (tp) tp[cl * n + k] = (T)p;
         if (wdiff) wdiff[cl * n + k] = (T)(p - 1.0 / n);

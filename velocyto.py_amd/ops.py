@@ -1914,7 +1914,11 @@ def prepare_markov_factored(indptr, indices, pval, embedding, sigma_D: float, si
     sval = torch.empty(nnz, dtype=torch.float64, device=dev)
     sdiag, kw, tot = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
     es = torch.empty((n, edim), dtype=compute_dtype, device=dev)
-    _lib.check(_lib.lib().vcy_prepare_markov_factored(ip.data_ptr(), ix.data_ptr(), pv.data_ptr(), emb.data_ptr(), edim, sval.data_ptr(), sdiag.data_ptr(),
+    # The chain depends on differences of coordinates only, the rounding of es to the compute type on their size: the kernels get the
+    # embedding with the midpoint of its bounding box taken off in f64 (the same on every rank of a sharded chain: each passes all
+    # cells), so that max |es| is half the extent whatever the origin.  MarkovFactors.embedding and dense() keep the caller's own.
+    centred = emb - 0.5 * (emb.min(0).values + emb.max(0).values)
+    _lib.check(_lib.lib().vcy_prepare_markov_factored(ip.data_ptr(), ix.data_ptr(), pv.data_ptr(), centred.data_ptr(), edim, sval.data_ptr(), sdiag.data_ptr(),
                                                       kw.data_ptr(), tot.data_ptr(), es.data_ptr(), n, float(sigma_D), float(sigma_W),
                                                       _DT[compute_dtype], _stream()), "prepare_markov_factored")
     # s in CSC form, diagonal included (index plumbing: one sort of the nnz + n coordinates by (column, row))
