@@ -45,6 +45,11 @@ typedef enum { VCY_LINEAR = 0, VCY_SQRT = 1, VCY_LOG10 = 2 } vcy_transform;
  * :372-378,469-473). */
 typedef enum {
     VCY_RULES_FULL = 0,
+    /* The partial rule of speedboosted.pyx:372-378: A = sign(t) sqrt(|t| + psc), 0 below |t| = 1e-16.  What it guarantees about the root:
+     * VCY_F32 and the other transforms: the unit's own root / logarithm.  VCY_SQRT on VCY_F64 in the vcy_coldeltacor_partial* entries: the
+     * f32-seeded root after ONE Newton correction, relative error of A at most 2^-44 (a priori 3.7 2^-46; the largest over 2^26 arguments
+     * in [2^-60, 2^60] is 2^-45.46, 179 ulps, mean 10 ulps: profiles/r07_valu_issue_f64.txt; the tests hold it to 2^-43.5); a pair's correlation moves by at most 2 x that x sqrt(sum A^2 / sum (A - mean A)^2) against the
+     * correctly rounded root - 2e-13 on count data, under the rounding of the G-term sums.  16 instructions per gene instead of 18.          */
     VCY_RULES_PARTIAL = 1,
     /* The partial rule with the pseudocount dropped: A = sign(t) sqrt|t| (0 at t == 0).  VCY_SQRT on VCY_F32 matrices in the
      * vcy_coldeltacor_partial* entries only (anything else: VCY_ERR_INVALID).  In f32 `|t| + psc` rounds to `|t|` for every
@@ -52,7 +57,11 @@ typedef enum {
      * psc / (2 sqrt|t|) per gene.  Three VALU instructions per gene instead of five: the caller opts in when psc is far
      * below the scale of the matrix (the Python layer: psc <= 1e-9, mean |e| >= 1e-4, no non-zero entry below 1e-20:
      * v_rsq_f32 reads denormal differences, |t| < 2^-126, as zero and the product would be infinite).                  */
-    VCY_RULES_PARTIAL_NOPSC = 2
+    VCY_RULES_PARTIAL_NOPSC = 2,
+    /* The partial rule with the two-correction root on VCY_SQRT / VCY_F64: A is the correctly rounded root except near ties (at most 1 ulp
+     * there) - the element VCY_RULES_PARTIAL had up to round 6, bit for bit.  On VCY_F32 and with the other transforms it IS
+     * VCY_RULES_PARTIAL (same kernels, same bits).  The Python layer passes it under literal=True / VELOCYTO_AMD_LITERAL_RULE=1.             */
+    VCY_RULES_PARTIAL_ROOT2 = 3
 } vcy_rules;
 
 typedef void *vcy_stream;  /* hipStream_t */
@@ -60,7 +69,9 @@ typedef void *vcy_stream;  /* hipStream_t */
 const char *vcy_last_error(void);
 /* 4 (round 6).  History: 1 -> 2: vcy_diffuse_step_factored gained `int prepared` before compute_dtype; vcy_gram and vcy_embedding_scaling added;
  * vcy_knn_pool_csr requires >= 4 stored elements.  2 -> 3: vcy_clock_probe and vcy_coldeltacor_full_linear added.  3 -> 4: vcy_coldeltacor_full_linear_workspace_bytes takes C_out (repair flags); vcy_gemm_nt added.  A binder refuses a library whose version it was not built
- * against (velocyto_amd/_lib.py: EXPECTED_ABI). */
+ * against (velocyto_amd/_lib.py: EXPECTED_ABI).  (Round 7 added the enumerator VCY_RULES_PARTIAL_ROOT2: no argument list changed and every
+ * value a version-4 caller passes is still accepted, so the version stays; such a caller's VCY_RULES_PARTIAL on VCY_SQRT / VCY_F64 now gets
+ * the one-correction root described at vcy_rules.) */
 int vcy_abi_version(void);
 /* Number of CUs / LDS bytes per workgroup of the current device (host query). */
 int vcy_device_info(int *cu_count, int *lds_bytes_per_block, int64_t *hbm_bytes);
@@ -95,8 +106,9 @@ int vcy_transpose(const void *src, void *dst, int64_t rows, int64_t cols, int64_
  * With `order`, rows of ixs / out / d are addressed by the cell numbers it holds, so C_out may be SMALLER than the
  * number of rows of ixs / out: only the listed cells are computed, the other rows of out are left untouched (a
  * cell-sharded rank computes the cells whose neighbours are all local while the halo exchange is in flight).
- * `rules` = VCY_RULES_PARTIAL reproduces the *partial kernels, VCY_RULES_FULL the branch
- * rules of the full kernels on an explicit neighbour list.                                */
+ * `rules` = VCY_RULES_PARTIAL reproduces the *partial kernels (VCY_RULES_PARTIAL_ROOT2: with the correctly
+ * rounded f64 root, see vcy_rules), VCY_RULES_FULL the branch rules of the full kernels on an explicit
+ * neighbour list.                                                                          */
 int vcy_coldeltacor_partial(const void *e, const void *d, const int32_t *ixs, void *out, const int32_t *order,
                             int64_t C, int64_t G, int64_t ld, int64_t cell0, int64_t C_out, int64_t d_row0,
                             int64_t nrndm, int transform, int rules, double psc, int dtype, vcy_stream stream);

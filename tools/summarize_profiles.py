@@ -68,7 +68,8 @@ for sfx, dname, ctype, chunk in (("", "f32", "float", 1536), ("_f64", "f64", "do
         continue
     pair_chunks = cells * nrndm * ((genes + chunk - 1) // chunk)
     kname = next(kn for (cn, kn) in acc if tagk in kn and cn == "SQ_INSTS_VALU")
-    rule = {"1": "partial (literal)", "2": "partial, pseudocount dropped (VCY_RULES_PARTIAL_NOPSC)", "0": "full"}.get(kname.split("<")[1].split(",")[2].strip(), "?")
+    rule = {"1": "partial (literal)", "2": "partial, pseudocount dropped (VCY_RULES_PARTIAL_NOPSC)", "0": "full",
+            "3": "partial (literal), two-correction f64 root (VCY_RULES_PARTIAL_ROOT2)"}.get(kname.split("<")[1].split(",")[2].strip(), "?")
     wc = cdc.get("SQ_WAVE_CYCLES")
     # GRBM_GUI_ACTIVE comes back summed over the 8 XCDs (each has its own GRBM; a single-XCD reading would be 18 "GHz"): cycles per ns per XCD
     ghz = cdc["GRBM_GUI_ACTIVE"] / dur["GRBM_GUI_ACTIVE"] / 8.0 if "GRBM_GUI_ACTIVE" in cdc else None

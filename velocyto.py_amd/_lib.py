@@ -21,7 +21,8 @@ ARCH = "gfx950"
 _lib = None
 
 c_i64, c_int, c_dbl, c_vp, c_sz = ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
-EXPECTED_ABI = 4                  # vcy_abi_version() of the header this table mirrors
+EXPECTED_ABI = 4                  # vcy_abi_version() of the header this table mirrors (still 4 with the enumerator VCY_RULES_PARTIAL_ROOT2 = 3,
+                                  # ops.RULES_PARTIAL_ROOT2: no argument list changed, `rules` stays a c_int)
 
 # name -> (restype, argtypes); mirrors include/velocyto_hip.h one to one
 SIGNATURES = {

@@ -67,7 +67,7 @@ template <> __device__ __forceinline__ float xform<float, VCY_SQRT, VCY_RULES_PA
     return copysignf(fast_sqrt<float>(fmaf(psc, c, fabsf(t))), t);
 }
 
-// f64 hot variant (partial sqrt; the reference-precision build).  sqrt(double) expands to v_rsq_f64 (12.5 clocks per wave64, measured:
+// f64 partial sqrt, two-correction root (VCY_RULES_PARTIAL_ROOT2; until round 7 the element of VCY_RULES_PARTIAL).  sqrt(double) expands to v_rsq_f64 (12.5 clocks per wave64, measured:
 // profiles/r03_valu_issue_f64.txt) + a coupled Goldschmidt step + two residual corrections, wrapped in a range scaling (inputs below
 // 2^-767) and a 0 / inf fix-up: ~17 f64 instructions, 130 clocks per element with the moments.  The argument here is |t| + psc with
 // |t| >= 1e-16 whenever the result is used, far inside the f32 exponent range, so the seed comes from the f32 unit instead:
@@ -79,7 +79,7 @@ template <> __device__ __forceinline__ float xform<float, VCY_SQRT, VCY_RULES_PA
 // result that is the correctly rounded root in all but near-tie cases (round 3: up to 2 ulp; tools/ubench/valu_issue_f64.hip counts
 // both over 2^26 arguments in [2^-60, 2^60], profiles/r04_valu_issue_f64.txt).  Domain: |t| + psc in [1e-38, 3e38] - a count-derived
 // matrix never leaves it, ops.check_f64_sqrt_domain refuses one that does, below 1e-16 the zero rule discards the value.
-// The element of the hot loop: that seed and those two Newton corrections (tools/ubench/valu_issue_f64.hip: sqrt_f32prod), with the zero rule of speedboosted.pyx:372 applied to
+// The element: that seed and those two Newton corrections (tools/ubench/valu_issue_f64.hip: sqrt_f32prod), with the zero rule of speedboosted.pyx:372 applied to
 // the ARGUMENT of the seed: v_rsq_f32(+inf) = +0, a y_f of 0 makes s0 = x_f y_f = 0 and h = y_f / 2 = 0 (halved in f32 here: an exponent
 // decrement of the converted value would turn a zero into -inf), both corrections add (x - 0) 0 and the root comes out as an exact 0 -
 // one v_cndmask on a 32-bit value where zeroing the finished double took two.  (The select sits before the v_rsq because the compiler
@@ -95,7 +95,7 @@ template <> __device__ __forceinline__ float xform<float, VCY_SQRT, VCY_RULES_PA
 // and the four f32 instructions of two elements in one asm block for the trans-use hazard: parity-green) 238.9 against 242.4 on its
 // box, 1.4 % - not kept; v_rsq_f64 on x itself with the rule on the high word of its result and both products in f64 (15 instructions, no
 // conversions) 237.4 against 231.2 on its box.
-template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_PARTIAL>(double t, double psc)
+template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_PARTIAL_ROOT2>(double t, double psc)
 {
     const double x = fabs(t) + psc;
     const float xf0 = (float)x;
@@ -107,6 +107,27 @@ template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_
     d = fma(-s1, s1, x);
     // (round 5: the sign as v_and_b32 + v_or_b32, 19 instructions: 241.0 against 235.0 ms; as one v_and_or_b32: 235.0 - it costs what v_bfi_b32 costs)
     return copysign(fma(d, h, s1), t);
+}
+
+// VCY_RULES_PARTIAL, the default f64 element: the same seed, zero rule and sign with ONE Newton correction - 16 instructions per element,
+// the second `d = x - s1^2`, `s1 + d h` pair (two v_fma_f64) left out.  Error of the root after the one correction, relative: with e0 the
+// error of the 24-bit seed s0 (the rounding of x to f32, 2^-24, half of it reaching the root; v_rsq_f32, 1 ulp; the rounding of the f32 product
+// x_f y_f: e0 <= 1.75 2^-23), e_h that of h against 1 / (2 sqrt x) (v_rsq_f32 + half the conversion's: <= 1.25 2^-23),
+//     s1 / sqrt x - 1 = -e0^2 / 2 + e0 e_h (1 + O(e0)) + the roundings of the two FMAs (2^-53 each, the first scaled by e0),
+// at most 3.7 2^-46 < 2^-44; tools/ubench/valu_issue_f64.hip (sqrt_seedzero1) measures 2^-45.46 at most over 2^26 arguments (179 ulps; mean 10 ulps) and the
+// element at 70.6 clocks against 77.4 (profiles/r07_valu_issue_f64.txt); stage D 205.6 against 230.5 ms in one call (profiles/r07_root1_vs_root2.txt).
+// Pearson's r of a pair moves by |dr| <= 2 delta sqrt(sum A^2 / sum (A - mean A)^2) for a relative element error delta (Cauchy-Schwarz, as in
+// ops.partial_rules_for): 2e-13 at delta = 2^-44 and the ratios of pooled count data (<= 2.5), 500 times below the f64 bar of 1e-10 and below the
+// a-priori bound of the G-term f64 accumulation itself.  VCY_RULES_PARTIAL_ROOT2 (below) keeps the two-correction root.
+template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_PARTIAL>(double t, double psc)
+{
+    const double x = fabs(t) + psc;
+    const float xf0 = (float)x;
+    const float xf = (fabs(t) < 1e-16) ? __builtin_inff() : xf0;
+    const float yf = __builtin_amdgcn_rsqf(xf);
+    const double s0 = (double)(xf0 * yf), h = (double)(0.5f * yf);
+    const double d = fma(-s0, s0, x);
+    return copysign(fma(d, h, s0), t);
 }
 
 // VCY_RULES_PARTIAL_NOPSC (f32, sqrt): A = sign(t) sqrt|t| as t * rsq|t| with the legacy multiply (0 * anything = 0: the zero
@@ -872,7 +893,8 @@ static int launch_partial(const void *e, const void *d, const void *d2, const in
         if (d2) {
             if constexpr (sizeof(T) == 8) {
                 // f64 dual control: 4 cells x 1024-gene chunks (three staged arrays of 8-byte elements: 96 KiB) - the single kernel's chunk
-                // length, hence its order of summation (real correlations bit-identical to the single launch) and its ratio of
+                // length, hence its order of summation of the pair moments (the d-moments are summed by four staging waves per member where the
+                // single launch has two: real correlations equal to the single launch up to that rounding, ~1e-16) and its ratio of
                 // reduction work per element; 6 cells x 768 (VCY_CDC_DUAL_F64=0) shares rows better but pays 12-element chunks
                 if (env_int("VCY_CDC_DUAL_F64", 1) == 1)
                     rc = launch_grouped<T, TR, RULES, GRP_GC_DUAL_F64, GRP_NV_F64, true>(e, d, d2, ixs, out, out2, order, G, ld, cell0, C_out, d_row0, nrndm, psc, st, fuse, dev, &done);
@@ -919,6 +941,11 @@ static int dispatch_partial(const void *e, const void *d, const void *d2, const 
 {
 #define VCY_CASE(TR, RU) \
     if (transform == TR && rules == RU) return launch_partial<T, TR, RU>(e, d, d2, ixs, out, out2, order, G, ld, cell0, C_out, d_row0, nrndm, psc, st, fuse);
+    // VCY_RULES_PARTIAL_ROOT2 names another root for the f64 sqrt element only: everywhere else it IS VCY_RULES_PARTIAL (same instance)
+    if (rules == VCY_RULES_PARTIAL_ROOT2) {
+        if constexpr (std::is_same<T, double>::value) { VCY_CASE(VCY_SQRT, VCY_RULES_PARTIAL_ROOT2) }
+        rules = VCY_RULES_PARTIAL;
+    }
     VCY_CASE(VCY_LINEAR, VCY_RULES_PARTIAL)
     VCY_CASE(VCY_LINEAR, VCY_RULES_FULL)
     VCY_CASE(VCY_SQRT, VCY_RULES_PARTIAL)

@@ -20,9 +20,10 @@ from . import _lib
 
 F32, F64, U16, U8 = 0, 1, 2, 3
 LINEAR, SQRT, LOG10 = 0, 1, 2
-RULES_FULL, RULES_PARTIAL, RULES_PARTIAL_NOPSC = 0, 1, 2
+RULES_FULL, RULES_PARTIAL, RULES_PARTIAL_NOPSC, RULES_PARTIAL_ROOT2 = 0, 1, 2, 3
 PSC_NEGLIGIBLE = 1e-9       # f32 sqrt: a pseudocount at or below this is a candidate for RULES_PARTIAL_NOPSC ...
-RULE_NAMES = {0: "full", 1: "partial (literal, speedboosted.pyx:372-378)", 2: "partial, pseudocount below f32 resolution dropped: sign(t) sqrt|t|"}
+RULE_NAMES = {0: "full", 1: "partial (literal, speedboosted.pyx:372-378)", 2: "partial, pseudocount below f32 resolution dropped: sign(t) sqrt|t|",
+              3: "partial (literal), f64 sqrt root with two Newton corrections (correctly rounded except near ties)"}
 SCALE_ORDINARY = 1e-4       # ... on a matrix whose mean |e| is at least this (psc / scale <= 1e-5, see partial_rules_for)
 TRANSFORMS = {"linear": LINEAR, "sqrt": SQRT, "log10": LOG10, "log": LOG10}
 
@@ -592,8 +593,8 @@ F64_SQRT_DOMAIN_MSG = "colDeltaCor sqrt transform in f64: |e| reaches {:.3g}, ou
 
 
 def check_f64_sqrt_domain(e: CellMatrix) -> None:
-    """The f64 partial-sqrt element (csrc/coldeltacor.hip, xform<double, SQRT, PARTIAL>) seeds its square root from the f32 unit: the
-    correctly rounded root in all but near-tie cases for arguments inside the f32 exponent range, NaN above 3.4e38 (the converted
+    """The f64 partial-sqrt elements (csrc/coldeltacor.hip, xform<double, SQRT, PARTIAL[_ROOT2]>) seed their square root from the f32 unit: the
+    root within 2^-44 (RULES_PARTIAL) or correctly rounded in all but near-tie cases (RULES_PARTIAL_ROOT2) for arguments inside the f32 exponent range, NaN above 3.4e38 (the converted
     argument is +inf, v_rsq_f32 of it is 0, and inf * 0 is NaN).  A count-derived matrix never comes near it; a matrix that does is
     refused here (one reduction, one device->host sync - the callers that decide the branch rule once per matrix come through here,
     ops.partial_rules_for; every `validate=True` call of the partial entry points, fused ones included, does too).  A matrix that
@@ -606,7 +607,8 @@ def check_f64_sqrt_domain(e: CellMatrix) -> None:
 
 
 def literal_rule_forced() -> bool:
-    """VELOCYTO_AMD_LITERAL_RULE=1: never pick the no-pseudocount form (the facade's `literal_rule` attribute does the same per object)."""
+    """VELOCYTO_AMD_LITERAL_RULE=1: never pick the no-pseudocount form (f32) or the one-correction root (f64) - the facade's `literal_rule`
+    attribute does the same per object."""
     import os
     return os.environ.get("VELOCYTO_AMD_LITERAL_RULE", "0") == "1"
 
@@ -623,6 +625,9 @@ def partial_rules_for(e: CellMatrix, transform: int, psc: float, stats: Optional
       * mean |e| >= 1e-4 (below that the pseudocount is a visible part of |t| + psc),
       * no non-zero |e| below 1e-20: v_rsq_f32 reads a denormal as zero, so t * rsq|t| of a difference below 2^-126 would be
         inf; differences of entries at or above 1e-20 are multiples of their ulp (> 1e-27) and stay in the normal range.
+    On an f64 matrix with the sqrt transform the choice is between two roots of the same rule: RULES_PARTIAL, whose root carries one
+    Newton correction (relative error of A at most 2^-44, measured 2^-45.46; 16 instructions per gene), and - under `literal=True` or
+    VELOCYTO_AMD_LITERAL_RULE=1 - RULES_PARTIAL_ROOT2, the two-correction root (correctly rounded except near ties; 18 instructions).
     `stats`: a precomputed abs_stats vector - sharded callers all-reduce it (sum, min, sum) so that every rank decides alike
     (distributed.all_reduce_abs_stats); `cells`: the number of cells the sums cover when it is not e.C.  `literal=True` or
     VELOCYTO_AMD_LITERAL_RULE=1 keeps the literal rule whatever the data.
@@ -632,9 +637,18 @@ def partial_rules_for(e: CellMatrix, transform: int, psc: float, stats: Optional
     pair moves by |dr| <= 2 ||delta||_2 / ||A - mean A||_2 to first order (Cauchy-Schwarz on the centred, normalised vectors),
     i.e. <= psc * sqrt(mean_g 1/|t_g|) / sd(A) over the genes with 0 < |t_g| < 2^24 psc: a few 1e-7 on count-scale data
     (measured 1.5e-7 over all 12.5 M pairs of the bench workload), and below the f32 tolerance of 1e-5 down to matrix scales of
-    1e-4 (tests/test_gpu_ops.py::test_partial_nopsc_rule_bound_on_scaled_matrices)."""
+    1e-4 (tests/test_gpu_ops.py::test_partial_nopsc_rule_bound_on_scaled_matrices).
+
+    The same argument bounds the f64 one-correction root.  A relative element error delta perturbs A by delta_g = delta A_g, so
+    ||delta||_2 <= delta ||A||_2 and |dr| <= 2 delta sqrt(sum A^2 / sum (A - mean A)^2) to first order.  At delta = 2^-44 and the
+    ratios of pooled count data (sqrt(...) <= 2.5) that is 2e-13: 500 times below the f64 bar of 1e-10 and below the a-priori
+    bound of the G-term f64 accumulation that the reference and this kernel both perform (G 2^-53 = 2^-38 relative at 30 000
+    genes).  The element errors are not aligned with the data, so the shift seen is far smaller (one ulp of r in emulation;
+    tests/test_gpu_cdc_root.py asserts the bound through the kernel)."""
     if transform == SQRT and e.dtype == torch.float64 and e.C and not domain_checked:     # (domain_checked: the caller ran check_f64_sqrt_domain on
         check_f64_sqrt_domain(e)                                                            #  the matrix itself - `e` may be a staging buffer, atlas.py)
+    if transform == SQRT and e.dtype == torch.float64 and (literal or literal_rule_forced()):
+        return RULES_PARTIAL_ROOT2
     if transform != SQRT or e.dtype != torch.float32 or not (0.0 <= float(psc) <= PSC_NEGLIGIBLE) or e.C == 0 or literal or literal_rule_forced():
         return RULES_PARTIAL
     st = abs_stats(e) if stats is None else stats
