@@ -324,6 +324,34 @@ int vcy_gene_quantiles(const void *M, const void *M2, const double *scale_a, con
                        const double *qs_host, int nq, double *out, void *workspace, int64_t C, int64_t G,
                        int64_t ld, int dtype, vcy_stream stream);
 
+/* The same order statistics for a matrix that is only ever seen as a sequence of cell blocks (the atlas path): an exact MSB-first
+ * radix select with 8-bit digits whose memory is O(genes).  A TARGET is one 0-based rank in every gene's sorted column of all
+ * n_total cells; numpy's percentile q needs the two targets lo = floor((n_total - 1) q / 100) and min(lo + 1, n_total - 1).
+ *   state: vcy_gene_select_state_bytes(G, ntargets) device bytes: (ntargets, G) uint64 key prefixes, then (ntargets, G) uint32 ranks.
+ *   hist:  vcy_gene_select_hist_bytes(G, ntargets) device bytes: (ntargets, G, 256) uint32 counts of the current digit.
+ * Protocol: vcy_gene_select_begin once; then for pass = 0 .. vcy_gene_select_passes(dtype) - 1 (4 for VCY_F32, 8 for VCY_F64):
+ * vcy_gene_select_count_block on EVERY block of cells (any order, any blocking), then vcy_gene_select_advance once; then
+ * vcy_gene_select_finish.  The counts are integers: blocking, block order and atomic order do not change a bit of the result, and
+ * cell-sharded callers add their histograms (as int32) between the last count_block and advance; in pass 0 only the first
+ * (G, 256) histogram is used, for every target.  Keys order -0.0 below +0.0, like vcy_gene_quantiles; NaN is not ordered.
+ * count_block: M (C, ld) cells-major of dtype; with M2 / scale_a / scale_b (all three or none; G fp64 each) the statistic is
+ * taken of M[c,g]/scale_a[g] + M2[c,g]/scale_b[g] evaluated in dtype, bit for bit the value vcy_gene_quantiles and the weights
+ * of vcy_fit_weighted see.  C <= 2^31 - 1 per call.
+ * begin: ranks_host (ntargets, host int64) in [0, n_total); n_total <= 2^31 - 1, the width of the counters (VCY_ERR_INVALID beyond).
+ * finish: out (nq, G) fp64 = numpy's _lerp of the values of targets lo_target[i], hi_target[i] (host int arrays) at fraction
+ * t_host[i] in [0, 1), the arithmetic of vcy_gene_quantiles.  ntargets <= 16, nq <= 16.                                        */
+int vcy_gene_select_digit_bits(void);
+int vcy_gene_select_passes(int dtype);
+size_t vcy_gene_select_state_bytes(int64_t G, int ntargets);
+size_t vcy_gene_select_hist_bytes(int64_t G, int ntargets);
+int vcy_gene_select_begin(void *state, void *hist, const int64_t *ranks_host, int ntargets, int64_t n_total, int64_t G, int dtype,
+                          vcy_stream stream);
+int vcy_gene_select_count_block(const void *M, const void *M2, const double *scale_a, const double *scale_b, const void *state,
+                                void *hist, int pass, int ntargets, int64_t C, int64_t G, int64_t ld, int dtype, vcy_stream stream);
+int vcy_gene_select_advance(void *state, void *hist, int pass, int ntargets, int64_t G, int dtype, vcy_stream stream);
+int vcy_gene_select_finish(const void *state, const int *lo_target, const int *hi_target, const double *t_host, int nq, int ntargets,
+                           double *out, int64_t G, int dtype, vcy_stream stream);
+
 /* estimation.fit_slope_weighted_offset / fit_slope_weighted / fit_slope_offset with the
  * binary or dense weights of VelocytoLoom.fit_gammas (estimation.py:191-264, 300-366;
  * analysis.py:1179-1257), solved exactly: weighted moments per gene in one pass, then the

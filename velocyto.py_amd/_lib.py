@@ -97,6 +97,15 @@ SIGNATURES = {
     "vcy_quantile_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_gene_quantiles": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_dbl), c_int, c_vp, c_vp, c_i64,
                                    c_i64, c_i64, c_int, c_vp]),
+    "vcy_gene_select_digit_bits": (c_int, []),
+    "vcy_gene_select_passes": (c_int, [c_int]),
+    "vcy_gene_select_state_bytes": (c_sz, [c_i64, c_int]),
+    "vcy_gene_select_hist_bytes": (c_sz, [c_i64, c_int]),
+    "vcy_gene_select_begin": (c_int, [c_vp, c_vp, ctypes.POINTER(c_i64), c_int, c_i64, c_i64, c_int, c_vp]),
+    "vcy_gene_select_count_block": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_gene_select_advance": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp]),
+    "vcy_gene_select_finish": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), c_int, c_int, c_vp, c_i64,
+                                       c_int, c_vp]),
     "vcy_gamma_weights": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_dbl, c_int, c_vp]),
     "vcy_prepare_markov": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_dbl, c_dbl, c_int, c_vp]),
     "vcy_row_sums": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),

@@ -12,7 +12,9 @@ same kernels as the resident path (bench.py `Pipeline`); what changes is where t
            (HaloPlan.fetch_ragged) and afterwards pool every row of e = Sx_sz they read themselves: no dense row ever
            crosses a link, e is sharded by construction, pcs / size factors travel as small vectors.
   A        vcy_knn_pool_csr merges the k + 1 sparse rows of a cell into a dense f32 row (LDS slab per wave), block by block.
-  B        fit_slope moments of the rank's own cells, summed over blocks, all-reduced (3 G doubles).
+  B        fit_slope moments of the rank's own cells, summed over blocks, all-reduced (3 G doubles).  AtlasPath(fit="maxmin_diag"):
+           velocyto's default weighted fit instead - its per-gene percentiles from an exact select streamed over the blocks
+           (ops.StreamedGeneQuantiles: integer histograms, all-reduced), then the weighted moments (10 G doubles) and the boxed solve.
   C + D    per block: e rows = [block | sampled neighbours outside the block], pooled on the spot when the matrices are not
            resident; vcy_coldeltacor_partial_fused on the block with renumbered neighbour lists.
 
@@ -81,7 +83,14 @@ class AtlasPath:
     def __init__(self, cS: ops.CsrCounts, cU: ops.CsrCounts, fS: torch.Tensor, fU: torch.Tensor, pcs: torch.Tensor, embedding: torch.Tensor, *,
                  c0: int = 0, C_total: Optional[int] = None, k: int = 30, n_neighbors: int = 500, sampled_fraction: float = 0.5,
                  sampling_probs=(0.5, 0.1), block_cells: int = 0, dtype=torch.float32, psc: float = 1e-10, seed: int = 15071990,
-                 knn: str = "auto"):
+                 knn: str = "auto", fit: str = "slope"):
+        """fit: how stage B fits gamma.  "slope" (the default): gamma = max(0, sum xy / sum xx), unweighted, no offset (fit_slope,
+        estimation.py:267-279).  "maxmin_diag" (or "default"): velocyto's default fit_gammas(weights="maxmin_diag", fit_offset=True)
+        (analysis.py:1179-1257), the recipe of VelocytoLoom.fit_gammas and ShardedLoom.fit_gammas, with the per-gene percentiles
+        taken by a streamed exact select (ops.StreamedGeneQuantiles): 9 walks over the pooled blocks in f32, 17 in f64."""
+        if fit not in ("slope", "maxmin_diag", "default"):
+            raise ValueError(f"AtlasPath: unknown fit={fit!r} (\"slope\", \"maxmin_diag\" or \"default\")")
+        self.fit = "slope" if fit == "slope" else "maxmin_diag"
         self.dev = dev = cS.indptr.device
         self.knn_mode = knn
         self.dtype = ops.resolve_dtype(dtype)
@@ -142,6 +151,11 @@ class AtlasPath:
         self.kp1 = self.k + 1
         self.corr = torch.empty((self.nloc, self.nrndm), dtype=self.dtype, device=dev)
         self.gamma = None
+        self.q = self.R2 = None            # fit="maxmin_diag": the offset and the weighted R2 of the fit (float32, like gamma)
+        self.fit_thresholds = None         # ... and its per-gene float64 thresholds {"denom_S", "denom_U", "down", "up"}
+        self.fit_moments = None            # ... and the all-reduced (10, G) moments they were solved from
+        self.select_state_bytes = 0        # ... and the bytes the streamed select held at its peak
+        self._in_buf = None                # the block whose own rows the staging buffers hold
         self.stage_ms = np.zeros(4)
         self._resident = None
         self._plan = None
@@ -198,7 +212,127 @@ class AtlasPath:
         self.peak_block_bytes = (self._ebuf.t.numel() + self._ubuf.t.numel()) * self._ebuf.t.element_size()
 
     # ------------------------------------------------------------------ one pass of the path
+    def _gather_facts(self, Sx_b: ops.CellMatrix, facts: dict) -> None:
+        """The scale facts of e = Sx_sz over ALL cells of ALL ranks, block by block, on the first walk over the data."""
+        if self.dtype == torch.float64:       # the f64 sqrt element's domain: max |Sx| of every pooled block - the matrix itself, never
+            lo, hi = Sx_b.t.aminmax()         # the staging buffer (its halo rows are not written yet on the first pass); judged after
+            m = torch.maximum(lo.abs(), hi.abs()).double().reshape(1)     # the all-reduce below, by every rank alike
+            facts["absmax"] = m if facts["absmax"] is None else torch.maximum(facts["absmax"], m)
+        st, abs_st = ops.abs_stats(Sx_b), facts["abs_st"]
+        facts["abs_st"] = st if abs_st is None else torch.stack([abs_st[0] + st[0], torch.minimum(abs_st[1], st[1]), abs_st[2] + st[2]])
+
+    def _decide_rules(self, facts: dict) -> None:
+        # stage D's branch rule is decided ONCE from whole-matrix reductions, all-reduced: identical on every rank and for
+        # every block size (a per-block or per-rank decision could differ on borderline data)
+        abs_st, absmax = facts["abs_st"], facts["absmax"]
+        if abs_st is None:                      # a rank without a block still takes part in the all-reduce: the neutral element
+            abs_st = torch.tensor([0.0, float("inf"), 0.0], dtype=torch.float64, device=self._ebuf.t.device)
+        stats = D.all_reduce_abs_stats(abs_st)
+        if self.dtype == torch.float64:
+            D.check_f64_sqrt_domain(torch.zeros(1, dtype=torch.float64, device=self._ebuf.t.device) if absmax is None else absmax)
+        self.rules = ops.partial_rules_for(self._ebuf, ops.SQRT, self.psc, stats=stats, cells=self.C, domain_checked=True)
+
+    # ------------------------------------------------------------------ stage B, velocyto's default fit, from streamed blocks
+    def _data_pass(self, i_pass: int, n_passes: int, use, ev, timed: bool, tms: List[float]) -> None:
+        """Walk number i_pass of n_passes over the rank's blocks: every block is pooled into the staging buffers - unless its rows are
+        there already: one block = resident mode, nothing is pooled twice - and handed to use(Sx_b, Ux_b); S and U share the walk.
+        The walks alternate their direction, so a walk starts on the block the one before ended on, and the last one runs forwards:
+        pass 2 then finds the last block in the buffers, as after fit="slope".  Times: pooling of the first walk -> tms[0] (stage A),
+        every later pooling and all use -> tms[1] (stage B)."""
+        nblk = len(self._plan)
+        order = range(nblk) if (n_passes - 1 - i_pass) % 2 == 0 else range(nblk - 1, -1, -1)
+        for bi in order:
+            b0, b1 = self._plan[bi][0], self._plan[bi][1]
+            nb = b1 - b0
+            ev[0].record()
+            Sx_b, Ux_b = self._ebuf.rows(0, nb), self._ubuf.rows(0, nb)
+            if self._in_buf != bi:
+                self._pool(self.cS, self.fS, slice(b0, b1), Sx_b)
+                self._pool(self.cU, self.fU, slice(b0, b1), Ux_b)
+                self._in_buf = bi
+            ev[1].record()
+            use(Sx_b, Ux_b)
+            ev[2].record()
+            if timed:
+                torch.cuda.synchronize()
+                tms[0 if i_pass == 0 else 1] += ev[0].elapsed_time(ev[1]); tms[1] += ev[1].elapsed_time(ev[2])
+
+    def _fit_maxmin_diag(self, ev, timed: bool, tms: List[float]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """fit_gammas(weights="maxmin_diag", fit_offset=True) (analysis.py:1179-1257) over blocks, in three phases of walks:
+        (1) percentiles [99.9, 100] of Sx and of Ux -> the denominators of VelocytoLoom._maxnorm_denominator; (2) percentiles
+        [2, 98] of Sx/dS + Ux/dU -> the binary weights' thresholds; (3) the weighted moments, all-reduced and solved in the box
+        (the recipe of ShardedLoom.fit_gammas).  Phases 1 and 2 take one walk per 8-bit digit of the key each."""
+        G, C = self.G, self.C
+        facts = {"abs_st": None, "absmax": None}
+        selS = ops.StreamedGeneQuantiles(G, [99.9, 100], C, self.dtype, self.dev)
+        selU = ops.StreamedGeneQuantiles(G, [99.9, 100], C, self.dtype, self.dev)
+        self.select_state_bytes = selS.state_bytes + selU.state_bytes
+        n_passes = 2 * selS.passes + 1
+        i_pass = 0
+
+        def end_pass(*sels):
+            ev[0].record()
+            for sel in sels:
+                sel.advance()
+            ev[1].record()
+            if timed:
+                torch.cuda.synchronize()
+                tms[1] += ev[0].elapsed_time(ev[1])
+
+        while not selS.done:
+            first = i_pass == 0 and self.rules is None
+
+            def use(Sx_b, Ux_b):
+                selS.add_block(Sx_b)
+                selU.add_block(Ux_b)
+                if first:
+                    self._gather_facts(Sx_b, facts)
+            self._data_pass(i_pass, n_passes, use, ev, timed, tms)
+            if first:
+                self._decide_rules(facts)
+            end_pass(selS, selU)
+            i_pass += 1
+        ev[0].record()
+        denom = lambda p: torch.where(p[0] == 0, torch.clamp(p[1], min=0.001), p[0]).contiguous()     # _maxnorm_denominator's rule
+        dS, dU = denom(selS.result()), denom(selU.result())
+        del selS, selU
+        selZ = ops.StreamedGeneQuantiles(G, [2, 98], C, self.dtype, self.dev, two=True)
+        self.select_state_bytes = max(self.select_state_bytes, selZ.state_bytes)
+        ev[1].record()
+        if timed:
+            torch.cuda.synchronize()
+            tms[1] += ev[0].elapsed_time(ev[1])
+        while not selZ.done:
+            self._data_pass(i_pass, n_passes, lambda Sx_b, Ux_b: selZ.add_block(Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU), ev, timed, tms)
+            end_pass(selZ)
+            i_pass += 1
+        th = selZ.result()
+        down, up = th[0].contiguous(), th[1].contiguous()
+        del selZ
+        self.fit_thresholds = {"denom_S": dS, "denom_U": dU, "down": down, "up": up}
+        moms = []
+
+        def use(Sx_b, Ux_b):
+            m = ops.fit_weighted_moments(Ux_b, Sx_b, 1, M=Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU, down=down, up=up)
+            moms[:] = [m if not moms else moms[0].add_(m)]
+        self._data_pass(i_pass, n_passes, use, ev, timed, tms)
+        ev[0].record()
+        mom = moms[0] if moms else torch.zeros((10, G), dtype=torch.float64, device=self.dev)
+        D.all_reduce_sum(mom)
+        self.fit_moments = mom
+        gamma, q, R2 = ops.fit_weighted_from_moments(mom, C, fit_offset=True, box_q=True, lo_gamma=1e-8, up_gamma_default=20.0)
+        gamma = torch.where(torch.isfinite(gamma), gamma, torch.zeros_like(gamma))                    # analysis.py:1260
+        self.q, self.R2 = q, R2
+        ev[1].record()
+        if timed:
+            torch.cuda.synchronize()
+            tms[1] += ev[0].elapsed_time(ev[1])
+        return gamma, q
+
     def run(self, timed: bool = False) -> torch.Tensor:
+        """One pass of the path; returns the rank's correlation rows.  timed=True adds the stages' milliseconds to stage_ms =
+        [A pooling, B fit, A kNN search, D].  With fit="maxmin_diag" stage B includes everything its extra walks over the data
+        cost, the re-pooling of the blocks in streamed mode too; only the first walk's pooling counts as stage A."""
         dev, G = self.dev, self.G
         if self._plan is None:
             self._plan_blocks()
@@ -214,46 +348,42 @@ class AtlasPath:
         if timed:
             torch.cuda.synchronize()
             tK = ev[0].elapsed_time(ev[1])
-        # ---- pass 1: A (pooling of the own cells) + B (fit_slope moments, estimation.py:267-279), block by block
-        mom = torch.zeros((3, G), dtype=torch.float64, device=dev)
-        abs_st = absmax = None
-        for (b0, b1, erows_out, ixs) in self._plan:
-            nb = b1 - b0
+        self._in_buf = None
+        if self.fit == "slope":
+            # ---- pass 1: A (pooling of the own cells) + B (fit_slope moments, estimation.py:267-279), block by block
+            mom = torch.zeros((3, G), dtype=torch.float64, device=dev)
+            facts = {"abs_st": None, "absmax": None}
+            for (b0, b1, erows_out, ixs) in self._plan:
+                nb = b1 - b0
+                ev[0].record()
+                Sx_b, Ux_b = self._ebuf.rows(0, nb), self._ubuf.rows(0, nb)
+                self._pool(self.cS, self.fS, slice(b0, b1), Sx_b)
+                self._pool(self.cU, self.fU, slice(b0, b1), Ux_b)
+                ev[1].record()
+                mom += ops.fit_slope_moments(Ux_b, Sx_b)
+                ev[2].record()
+                if self.rules is None:                    # first pass only
+                    self._gather_facts(Sx_b, facts)
+                if timed:
+                    torch.cuda.synchronize()
+                    tA += ev[0].elapsed_time(ev[1]); tB += ev[1].elapsed_time(ev[2])
+            if self.rules is None:
+                self._decide_rules(facts)
             ev[0].record()
-            Sx_b, Ux_b = self._ebuf.rows(0, nb), self._ubuf.rows(0, nb)
-            self._pool(self.cS, self.fS, slice(b0, b1), Sx_b)
-            self._pool(self.cU, self.fU, slice(b0, b1), Ux_b)
+            D.all_reduce_sum(mom)
+            gamma = ops.fit_slope_from_moments(mom)
+            gamma[~torch.isfinite(gamma)] = 0.0          # fit_gammas' policy for genes without signal (analysis.py:1260); NaN would poison every d[c]
             ev[1].record()
-            mom += ops.fit_slope_moments(Ux_b, Sx_b)
-            ev[2].record()
-            if self.rules is None:                    # first pass only: the scale facts of e = Sx_sz over ALL cells of ALL ranks
-                if self.dtype == torch.float64:       # the f64 sqrt element's domain: max |Sx| of every pooled block - the matrix itself, never
-                    lo, hi = Sx_b.t.aminmax()         # the staging buffer (its halo rows are not written yet on the first pass); judged after
-                    m = torch.maximum(lo.abs(), hi.abs()).double().reshape(1)     # the all-reduce below, by every rank alike
-                    absmax = m if absmax is None else torch.maximum(absmax, m)
-                st = ops.abs_stats(Sx_b)
-                abs_st = st if abs_st is None else torch.stack([abs_st[0] + st[0], torch.minimum(abs_st[1], st[1]), abs_st[2] + st[2]])
             if timed:
                 torch.cuda.synchronize()
-                tA += ev[0].elapsed_time(ev[1]); tB += ev[1].elapsed_time(ev[2])
-        if self.rules is None:
-            # stage D's branch rule is decided ONCE from whole-matrix reductions, all-reduced: identical on every rank and for
-            # every block size (a per-block or per-rank decision could differ on borderline data)
-            if abs_st is None:                      # a rank without a block still takes part in the all-reduce: the neutral element
-                abs_st = torch.tensor([0.0, float("inf"), 0.0], dtype=torch.float64, device=self._ebuf.t.device)
-            stats = D.all_reduce_abs_stats(abs_st)
-            if self.dtype == torch.float64:
-                D.check_f64_sqrt_domain(torch.zeros(1, dtype=torch.float64, device=self._ebuf.t.device) if absmax is None else absmax)
-            self.rules = ops.partial_rules_for(self._ebuf, ops.SQRT, self.psc, stats=stats, cells=self.C, domain_checked=True)
-        ev[0].record()
-        D.all_reduce_sum(mom)
-        gamma = ops.fit_slope_from_moments(mom)
-        gamma[~torch.isfinite(gamma)] = 0.0          # fit_gammas' policy for genes without signal (analysis.py:1260); NaN would poison every d[c]
+                tB += ev[0].elapsed_time(ev[1])
+            q = None
+        else:                                        # the same stages A + B with velocyto's default fit: 2 x passes + 1 walks over the blocks
+            tms = [0.0, 0.0]
+            gamma, q = self._fit_maxmin_diag(ev, timed, tms)
+            assert self._in_buf == len(self._plan) - 1
+            tA += tms[0]; tB += tms[1]
         self.gamma = gamma
-        ev[1].record()
-        if timed:
-            torch.cuda.synchronize()
-            tB += ev[0].elapsed_time(ev[1])
         # ---- pass 2: C + D per block.  e rows = [block | sampled neighbours outside the block].  The blocks are walked
         #      backwards: the block pass 1 pooled last is still in the buffers and is not pooled again (one block = resident
         #      mode: nothing is pooled twice, only the halo rows are added)
@@ -266,7 +396,7 @@ class AtlasPath:
                 self._pool(self.cU, self.fU, slice(b0, b1), Ux_b)
             self._pool(self.cS, self.fS, erows_out, e_buf.rows(nb, nb + n_out))
             ev[1].record()
-            ops.coldeltacor_partial_fused(e_buf, Ux_b, gamma, None, ixs, ops.SQRT, self.rules, self.psc, cell0=0, u_row0=0,
+            ops.coldeltacor_partial_fused(e_buf, Ux_b, gamma, q, ixs, ops.SQRT, self.rules, self.psc, cell0=0, u_row0=0,
                                           out=self.corr[b0:b1], validate=False)
             ev[2].record()
             if timed:
@@ -284,9 +414,12 @@ class AtlasPath:
 
 
 def memory_plan(C: int, G: int, nnz_per_cell: float, world: int, block_cells: int, nrndm: int = 250, k: int = 30, count_bytes: int = 1,
-                elem_bytes: int = 4, halo_e: float = 0.1, halo_k: float = 0.25) -> Dict[str, float]:
+                elem_bytes: int = 4, halo_e: float = 0.1, halo_k: float = 0.25, fit: str = "slope") -> Dict[str, float]:
     """Bytes one rank holds (GB).  halo_e / halo_k: E and count-row halos as fractions of the rank's own cells (measured:
-    tools/halo_fraction.py, AtlasPath.n_e_halo / n_count_halo)."""
+    tools/halo_fraction.py, AtlasPath.n_e_halo / n_count_halo).  fit="maxmin_diag" adds the state of the streamed select at its
+    peak (phase 1: three ranks - both of percentile 99.9 and the maximum - of Sx and of Ux): per (rank, gene) a 256-bin uint32
+    histogram, an 8-byte key prefix and a 4-byte rank; it does not grow with the cell count."""
+    select = 0 if fit == "slope" else 2 * 3 * G * (256 * 4 + 8 + 4)
     nloc = math.ceil(C / world)
     ld = ops.padded_ld(G)
     blk = min(block_cells if block_cells > 0 else nloc, nloc)
@@ -295,8 +428,8 @@ def memory_plan(C: int, G: int, nnz_per_cell: float, world: int, block_cells: in
     gb = lambda x: x / 1e9
     return {"cells_per_rank": nloc, "csr_layers_with_halo_GB": gb(csr), "pcs_embedding_replicated_GB": gb(C * 32 * 8),
             "graph_and_neighbour_lists_GB": gb(nloc * (1 + halo_e) * (k + 1) * 8 + nloc * nrndm * 4), "block_Sx_Ux_GB": gb(dense_block),
-            "corr_rows_GB": gb(nloc * nrndm * elem_bytes), "kNN_workspace_GB": gb(8192 * C * 4),
-            "total_GB": gb(csr + C * 32 * 8 + dense_block + nloc * nrndm * (4 + elem_bytes) + 8192 * C * 4)}
+            "corr_rows_GB": gb(nloc * nrndm * elem_bytes), "kNN_workspace_GB": gb(8192 * C * 4), "fit_select_histograms_GB": gb(select),
+            "total_GB": gb(csr + C * 32 * 8 + dense_block + nloc * nrndm * (4 + elem_bytes) + 8192 * C * 4 + select)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

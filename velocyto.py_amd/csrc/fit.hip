@@ -10,6 +10,7 @@
 // closed form -- the problems the reference hands to nnls / Brent / L-BFGS-B are 1- or
 // 2-parameter convex quadratics over a box.  HBM-bound: 2 * G * s bytes per cell (plain fit).
 #include <math.h>
+#include <algorithm>
 #include "common.h"
 
 namespace vcy {
@@ -312,6 +313,18 @@ template <> struct Key<double> {
     static __device__ __forceinline__ double dec(U u) { u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u; return __longlong_as_double((long long)u); }
 };
 
+// numpy's _lerp between two order statistics a = v[lo], b = v[lo + 1] at fraction t, without fma contraction so that the rounding
+// matches numpy's mul-then-add; t == 0 returns a itself (also when b is infinite).  Shared by every percentile kernel of this file.
+__device__ __forceinline__ double lerp_numpy(double a, double b, double t)
+{
+#pragma clang fp contract(off)   // hipcc would fuse the mul/add below even through the *_rn intrinsics
+    const double diff = __dsub_rn(b, a);
+    double r = __dadd_rn(a, __dmul_rn(diff, t));
+    if (t >= 0.5) r = __dsub_rn(b, __dmul_rn(diff, __dsub_rn(1.0, t)));
+    if (t == 0.0) r = a;
+    return r;
+}
+
 // One histogram increment per matching lane.  Expression rows are mostly exact zeros and a row's values share a few exponents, so the
 // lanes of a wave mostly ask for the SAME bin - and LDS atomics on one address serialise, 64 deep when a whole wave holds zeros (the 2nd
 // percentile of a 60 %-zero matrix cost twice the 98th).  The lanes that share the first matching lane's digit are therefore folded
@@ -427,15 +440,9 @@ __global__ __launch_bounds__(256) void k_gene_quantiles(const T *__restrict__ Z,
         if ((tid & 63) == 0) { atomicAdd(&s_cnt_le, cnt); atomicMin(&s_min_gt, mg); }
         __syncthreads();
         if (tid == 0) {
-#pragma clang fp contract(off)   // hipcc would fuse the mul/add below even through the *_rn intrinsics
             T vhi = vlo;
             if (lo + 1 < nvalid && s_cnt_le < (unsigned)(lo + 2)) vhi = Key<T>::dec((U)s_min_gt);
-            // numpy _lerp, without fma contraction so the rounding matches numpy's mul-then-add
-            const double a = (double)vlo, b = (double)vhi, diff = __dsub_rn(b, a);
-            double r = __dadd_rn(a, __dmul_rn(diff, t));
-            if (t >= 0.5) r = __dsub_rn(b, __dmul_rn(diff, __dsub_rn(1.0, t)));
-            if (t == 0.0) r = a;
-            out[(int64_t)qi * G + g] = r;
+            out[(int64_t)qi * G + g] = lerp_numpy((double)vlo, (double)vhi, t);
         }
         __syncthreads();
     }
@@ -571,17 +578,133 @@ __global__ __launch_bounds__(1024) void k_gene_quantiles_reg(const T *__restrict
         if ((tid & 63) == 0) { atomicAdd(&s_cnt_le, cnt); atomicMin(&s_min_gt, mg); }
         __syncthreads();
         if (tid == 0) {
-#pragma clang fp contract(off)   // hipcc would fuse the mul/add below even through the *_rn intrinsics
             T vhi = vlo;
             if (lo + 1 < nvalid && s_cnt_le < (unsigned)(lo + 2)) vhi = Key<T>::dec((U)s_min_gt);
-            // numpy _lerp, without fma contraction so the rounding matches numpy's mul-then-add
-            const double a = (double)vlo, b = (double)vhi, diff = __dsub_rn(b, a);
-            double r = __dadd_rn(a, __dmul_rn(diff, t));
-            if (t >= 0.5) r = __dsub_rn(b, __dmul_rn(diff, __dsub_rn(1.0, t)));
-            if (t == 0.0) r = a;
-            out[(int64_t)qi * G + g] = r;
+            out[(int64_t)qi * G + g] = lerp_numpy((double)vlo, (double)vhi, t);
         }
         __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- streamed per-gene order statistics
+// The same exact selection for a matrix that is only ever seen as a sequence of cell blocks (the atlas path): memory O(genes).
+// A TARGET is one rank of one gene's sorted column; per (target, gene) the state is the key prefix fixed so far and the rank
+// left among the keys that share it.  One digit pass over the data = k_select_count on every block (adds the block's counts
+// of the current 8-bit digit, per target restricted to the keys matching its prefix, into a global (targets, G, 256)
+// histogram of integers), then k_select_advance (scans a histogram, fixes the digit, updates the rank).  sizeof(key)
+// passes: 4 over f32 data, 8 over f64.  The counts are integers, so neither the blocking, the order of the blocks, the
+// order of the atomics nor a sum over ranks changes a bit of the result.  Both ranks of a percentile (lo, lo + 1) are
+// targets of the same passes; k_select_finish interpolates like k_gene_quantiles (lerp_numpy).
+//
+// k_select_count: a workgroup of 16 waves takes a slab of 64 genes x a range of at most SEL_MAXCELLS cells.  Lane <-> gene
+// (a wave reads one 256/512-byte row segment per cell), waves interleave the cells.  The slab's histograms live in LDS as
+// [target][bin pair][gene], two 16-bit counters to the word (a range never holds 2^16 cells), gene stride 65: the lanes of a
+// counting wave (64 genes, one bin each) and the lanes of a flushing wave (64 bin pairs of one gene) both fall in 64
+// different banks.  LDS adds are the native ds_add_u32; a wave's lanes never share a word, waves may.  Up to 4 targets per
+// launch: 4 x 33 280 B of the CU's 160 KiB.  Non-empty counters are flushed with device-scope integer atomics, a wave's
+// going to consecutive bins of one gene.  In the first pass every target has the same (empty) prefix: target 0 is counted
+// alone and k_select_advance reads its histogram for all.
+constexpr int SEL_GENES = 64, SEL_GSTRIDE = 65, SEL_WAVES = 16, SEL_MAXT = 4, SEL_MAXCELLS = 32768, SEL_MAXTARGETS = 16;
+constexpr size_t SEL_LDS_PER_TARGET = (size_t)128 * SEL_GSTRIDE * sizeof(unsigned);
+
+template <typename T, int NT, bool TWO>
+__global__ __launch_bounds__(64 * SEL_WAVES) void k_select_count(const T *__restrict__ M, const T *__restrict__ M2,
+                                                                  const double *__restrict__ scale_a, const double *__restrict__ scale_b,
+                                                                  const uint64_t *__restrict__ prefix, unsigned *__restrict__ hist, int pass,
+                                                                  int C, int per, int G, int64_t ld)
+{
+    using U = typename Key<T>::U;
+    constexpr int PASSES = sizeof(U);
+    constexpr int UNR = 8;                                         // cells a wave has in flight: their loads are issued before the first is used
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned *cnt = reinterpret_cast<unsigned *>(smem);            // [NT][128][SEL_GSTRIDE]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g0 = blockIdx.x * SEL_GENES, g = g0 + lane;
+    const int c0 = blockIdx.y * per, c1 = min(C, c0 + per);
+    for (int i = tid; i < NT * 128 * SEL_GSTRIDE; i += 64 * SEL_WAVES) cnt[i] = 0;
+    __syncthreads();
+    const int shift = 8 * (PASSES - 1 - pass);
+    if (g < G) {
+        U pf[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) pf[t] = pass == 0 ? (U)0 : (U)(prefix[(int64_t)t * G + g] >> (shift + 8));
+        T den_a = T(1), den_b = T(1);
+        if (TWO) { den_a = (T)scale_a[g]; den_b = (T)scale_b[g]; }
+        for (int cb = c0 + wave; cb < c1; cb += SEL_WAVES * UNR) {
+            T m[UNR], m2[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                // branch-free: a cell beyond the range re-reads the range's last row (inside the block) and is dropped below
+                const int64_t o = (int64_t)min(cb + u * SEL_WAVES, c1 - 1) * ld + g;
+                m[u] = M[o];
+                m2[u] = TWO ? M2[o] : T(0);
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                if (cb + u * SEL_WAVES >= c1) break;
+                const U k = Key<T>::enc(zvalue<T>(m[u], m2[u], den_a, den_b, TWO));
+                const unsigned d = (unsigned)((k >> shift) & 0xff);
+                const U hi = pass == 0 ? (U)0 : (U)(k >> ((shift + 8) & (8 * PASSES - 1)));
+                const unsigned inc = 1u << ((d & 1) * 16);
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (hi == pf[t]) atomicAdd(&cnt[(t * 128 + (int)(d >> 1)) * SEL_GSTRIDE + lane], inc);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < NT * SEL_GENES * 128; i += 64 * SEL_WAVES) {
+        const int bp = i & 127, gl = (i >> 7) & (SEL_GENES - 1), t = i >> 13;
+        const unsigned v = cnt[(t * 128 + bp) * SEL_GSTRIDE + gl];
+        if (v != 0 && g0 + gl < G) {
+            unsigned *h = hist + ((int64_t)t * G + (g0 + gl)) * 256 + 2 * bp;
+            if (v & 0xffffu) atomicAdd(h, v & 0xffffu);
+            if (v >> 16) atomicAdd(h + 1, v >> 16);
+        }
+    }
+}
+
+// One wave per (target, gene): scan the 256 bins (4 per lane, as k_gene_quantiles does), fix the digit that holds the rank.
+// A rank beyond the histogram's total (cells missing from the pass) selects nothing and leaves the state as it was.
+__global__ __launch_bounds__(256) void k_select_advance(uint64_t *__restrict__ prefix, unsigned *__restrict__ rank,
+                                                         const unsigned *__restrict__ hist, int shift, int shared_hist, int NT, int G)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t tg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tg >= (int64_t)NT * G) return;
+    const unsigned *h = hist + (shared_hist ? tg % G : tg) * 256 + lane * 4;
+    const unsigned h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3];
+    const unsigned tot = h0 + h1 + h2 + h3;
+    unsigned incl = tot;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    const unsigned excl = incl - tot, rk = rank[tg];
+    if (rk >= excl && rk < incl) {   // at most one lane
+        unsigned r = rk - excl;
+        int d;
+        if (r < h0) d = 0;
+        else if ((r -= h0) < h1) d = 1;
+        else if ((r -= h1) < h2) d = 2;
+        else { r -= h2; d = 3; }
+        prefix[tg] |= (uint64_t)(lane * 4 + d) << shift;
+        rank[tg] = r;
+    }
+}
+
+struct SelArgs { double t[16]; int ilo[16], ihi[16]; };   // per percentile: interpolation fraction, targets of v[lo] and v[lo + 1]
+
+template <typename T>
+__global__ void k_select_finish(const uint64_t *__restrict__ prefix, SelArgs sa, int nq, double *__restrict__ out, int G)
+{
+    using U = typename Key<T>::U;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    for (int qi = 0; qi < nq; ++qi) {
+        const T vlo = Key<T>::dec((U)prefix[(int64_t)sa.ilo[qi] * G + g]), vhi = Key<T>::dec((U)prefix[(int64_t)sa.ihi[qi] * G + g]);
+        out[(int64_t)qi * G + g] = lerp_numpy((double)vlo, (double)vhi, sa.t[qi]);
     }
 }
 
@@ -766,6 +889,131 @@ extern "C" int vcy_gene_quantiles(const void *M, const void *M2, const double *s
         else if (reg && C <= 1024 * 50) VCY_QREG(double, 50);          // 100 of the 128 VGPRs a 1024-thread workgroup may use hold keys
         else hipLaunchKernelGGL(k_gene_quantiles<double>, dim3((unsigned)G), dim3(256), 0, st, (const double *)Z, qs_dev, nq, out, (int)C, (int)G, mask_mode != 0);
     }
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+// ---- streamed order statistics: the state is (ntargets, G) uint64 prefixes followed by (ntargets, G) uint32 ranks
+extern "C" int vcy_gene_select_digit_bits(void) { return 8; }
+extern "C" int vcy_gene_select_passes(int dtype) { return dtype == VCY_F32 ? 4 : (dtype == VCY_F64 ? 8 : 0); }
+extern "C" size_t vcy_gene_select_state_bytes(int64_t G, int ntargets) { return (size_t)ntargets * (size_t)G * (sizeof(uint64_t) + sizeof(unsigned)); }
+extern "C" size_t vcy_gene_select_hist_bytes(int64_t G, int ntargets) { return (size_t)ntargets * (size_t)G * 256 * sizeof(unsigned); }
+
+static int select_args_ok(const void *state, const void *hist, int ntargets, int64_t G, int dtype)
+{
+    VCY_REQUIRE(state && hist, "gene_select: null pointer");
+    VCY_REQUIRE(ntargets > 0 && ntargets <= SEL_MAXTARGETS, "gene_select: ntargets outside [1,16]");
+    VCY_REQUIRE(G > 0 && G <= INT32_MAX / 2, "gene_select: bad gene count");
+    VCY_REQUIRE(dtype == VCY_F32 || dtype == VCY_F64, "gene_select: bad dtype");
+    return VCY_OK;
+}
+
+extern "C" int vcy_gene_select_begin(void *state, void *hist, const int64_t *ranks_host, int ntargets, int64_t n_total, int64_t G,
+                                     int dtype, vcy_stream stream)
+{
+    int rc = select_args_ok(state, hist, ntargets, G, dtype);
+    if (rc) return rc;
+    VCY_REQUIRE(ranks_host, "gene_select_begin: null pointer");
+    // the counters are 32-bit (and are summed over ranks as int32): every count is at most the total cell number
+    VCY_REQUIRE(n_total > 0 && n_total <= INT32_MAX, "gene_select_begin: the total cell number must be in [1, 2^31 - 1] (32-bit counts)");
+    for (int t = 0; t < ntargets; ++t) VCY_REQUIRE(ranks_host[t] >= 0 && ranks_host[t] < n_total, "gene_select_begin: rank outside [0, n_total)");
+    hipStream_t st = as_stream(stream);
+    uint64_t *prefix = (uint64_t *)state;
+    unsigned *rank = (unsigned *)(prefix + (size_t)ntargets * G);
+    VCY_CHECK_HIP(hipMemsetAsync(prefix, 0, (size_t)ntargets * G * sizeof(uint64_t), st));
+    VCY_CHECK_HIP(hipMemsetAsync(hist, 0, vcy_gene_select_hist_bytes(G, ntargets), st));
+    for (int t = 0; t < ntargets; ++t)      // hipMemsetD32Async: one 32-bit pattern per target row, no host buffer to keep alive
+        VCY_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(rank + (size_t)t * G), (int)ranks_host[t], (size_t)G, st));
+    return VCY_OK;
+}
+
+template <typename T>
+static int select_count_launch(const void *M, const void *M2, const double *scale_a, const double *scale_b, const uint64_t *prefix,
+                               unsigned *hist, int pass, int nt, int64_t C, int64_t G, int64_t ld, hipStream_t st)
+{
+    DevInfo di;
+    int rc = device_info(&di);
+    if (rc) return rc;
+    const int64_t slabs = (G + SEL_GENES - 1) / SEL_GENES;
+    // cell ranges: short enough for the 16-bit LDS counters, and enough of them that the grid covers the CUs four times over
+    int64_t nsplit = std::max<int64_t>((C + SEL_MAXCELLS - 1) / SEL_MAXCELLS, (4 * (int64_t)di.cus + slabs - 1) / slabs);
+    nsplit = std::min<int64_t>(std::max<int64_t>(nsplit, 1), (C + 63) / 64);      // ... but no range below 64 cells (the flush is per range)
+    const int64_t per = (C + nsplit - 1) / nsplit;
+    VCY_REQUIRE(per <= SEL_MAXCELLS, "gene_select_count_block: cell range too long");
+    const dim3 grid((unsigned)slabs, (unsigned)((C + per - 1) / per));
+    VCY_REQUIRE(grid.y <= 65535, "gene_select_count_block: block of cells too large for one launch");
+    const size_t lds = (size_t)nt * SEL_LDS_PER_TARGET;
+#define VCY_SEL(NT)                                                                                                              \
+    {                                                                                                                            \
+        auto kern = M2 ? k_select_count<T, NT, true> : k_select_count<T, NT, false>;                                             \
+        rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);                                                      \
+        if (rc) return rc;                                                                                                       \
+        hipLaunchKernelGGL(kern, grid, dim3(64 * SEL_WAVES), lds, st, (const T *)M, (const T *)M2, scale_a, scale_b, prefix, hist, pass, \
+                           (int)C, (int)per, (int)G, ld);                                                                        \
+    }
+    if (nt == 1) VCY_SEL(1) else if (nt == 2) VCY_SEL(2) else if (nt == 3) VCY_SEL(3) else VCY_SEL(4)
+#undef VCY_SEL
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_gene_select_count_block(const void *M, const void *M2, const double *scale_a, const double *scale_b, const void *state,
+                                           void *hist, int pass, int ntargets, int64_t C, int64_t G, int64_t ld, int dtype,
+                                           vcy_stream stream)
+{
+    int rc = select_args_ok(state, hist, ntargets, G, dtype);
+    if (rc) return rc;
+    VCY_REQUIRE(M, "gene_select_count_block: null pointer");
+    VCY_REQUIRE(C > 0 && C <= INT32_MAX && ld >= G, "gene_select_count_block: bad shape");
+    VCY_REQUIRE((scale_a == nullptr) == (scale_b == nullptr) && (scale_a == nullptr) == (M2 == nullptr), "gene_select_count_block: scale_a/scale_b/M2 go together");
+    VCY_REQUIRE(pass >= 0 && pass < vcy_gene_select_passes(dtype), "gene_select_count_block: pass outside [0, passes)");
+    hipStream_t st = as_stream(stream);
+    const uint64_t *prefix = (const uint64_t *)state;
+    // first pass: one histogram for all targets; later: groups of up to SEL_MAXT targets (each group reads the block once)
+    const int n = pass == 0 ? 1 : ntargets;
+    for (int t0 = 0; t0 < n; t0 += SEL_MAXT) {
+        const int nt = std::min(SEL_MAXT, n - t0);
+        unsigned *h = (unsigned *)hist + (size_t)t0 * G * 256;
+        rc = dtype == VCY_F32 ? select_count_launch<float>(M, M2, scale_a, scale_b, prefix + (size_t)t0 * G, h, pass, nt, C, G, ld, st)
+                              : select_count_launch<double>(M, M2, scale_a, scale_b, prefix + (size_t)t0 * G, h, pass, nt, C, G, ld, st);
+        if (rc) return rc;
+    }
+    return VCY_OK;
+}
+
+extern "C" int vcy_gene_select_advance(void *state, void *hist, int pass, int ntargets, int64_t G, int dtype, vcy_stream stream)
+{
+    int rc = select_args_ok(state, hist, ntargets, G, dtype);
+    if (rc) return rc;
+    const int passes = vcy_gene_select_passes(dtype);
+    VCY_REQUIRE(pass >= 0 && pass < passes, "gene_select_advance: pass outside [0, passes)");
+    hipStream_t st = as_stream(stream);
+    uint64_t *prefix = (uint64_t *)state;
+    unsigned *rank = (unsigned *)(prefix + (size_t)ntargets * G);
+    const int64_t tg = (int64_t)ntargets * G;
+    hipLaunchKernelGGL(k_select_advance, dim3((unsigned)((tg + 3) / 4)), dim3(256), 0, st, prefix, rank, (const unsigned *)hist,
+                       8 * (passes - 1 - pass), pass == 0 ? 1 : 0, ntargets, (int)G);
+    VCY_LAUNCH_CHECK();
+    VCY_CHECK_HIP(hipMemsetAsync(hist, 0, vcy_gene_select_hist_bytes(G, pass == 0 ? 1 : ntargets), st));
+    return VCY_OK;
+}
+
+extern "C" int vcy_gene_select_finish(const void *state, const int *lo_target, const int *hi_target, const double *t_host, int nq,
+                                      int ntargets, double *out, int64_t G, int dtype, vcy_stream stream)
+{
+    int rc = select_args_ok(state, state, ntargets, G, dtype);
+    if (rc) return rc;
+    VCY_REQUIRE(lo_target && hi_target && t_host && out && nq > 0 && nq <= 16, "gene_select_finish: bad arguments");
+    SelArgs sa;
+    for (int i = 0; i < 16; ++i) {
+        const bool in = i < nq;
+        if (in) VCY_REQUIRE(lo_target[i] >= 0 && lo_target[i] < ntargets && hi_target[i] >= 0 && hi_target[i] < ntargets &&
+                            t_host[i] >= 0.0 && t_host[i] < 1.0, "gene_select_finish: target or fraction out of range");
+        sa.t[i] = in ? t_host[i] : 0.0; sa.ilo[i] = in ? lo_target[i] : 0; sa.ihi[i] = in ? hi_target[i] : 0;
+    }
+    hipStream_t st = as_stream(stream);
+    if (dtype == VCY_F32) hipLaunchKernelGGL(k_select_finish<float>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const uint64_t *)state, sa, nq, out, (int)G);
+    else hipLaunchKernelGGL(k_select_finish<double>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const uint64_t *)state, sa, nq, out, (int)G);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
 }

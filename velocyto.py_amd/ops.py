@@ -11,7 +11,8 @@ vector starts 256-byte aligned).  This is the transpose of the reference's ``(G,
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Sequence, Tuple
+import math
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -1523,6 +1524,114 @@ def gene_quantiles(M: CellMatrix, qs: Sequence[float], M2: Optional[CellMatrix] 
                                              qs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(qs), out.data_ptr(), ws.data_ptr(),
                                              M.C, M.G, M.ld, M.code, _stream()), "gene_quantiles")
     return out
+
+
+def percentile_targets(qs: Sequence[float], n: int) -> Tuple[List[int], List[int], List[int], List[float]]:
+    """numpy.percentile's default ('linear') rule over n values, as ranks: per percentile q, h = (n - 1) * (q / 100), lo = floor(h),
+    hi = min(lo + 1, n - 1), t = h - lo (the arithmetic of vcy_gene_quantiles, in float64).  Returns (ranks, lo_target, hi_target, t):
+    the distinct ranks in ascending order and, per percentile, the positions of its two ranks in that list and its fraction."""
+    qs = [float(q) for q in np.asarray(qs, dtype=np.float64).ravel()]
+    if not qs or len(qs) > 16:
+        raise ValueError("percentile_targets: between 1 and 16 percentiles")
+    if n < 1:
+        raise ValueError("percentile_targets: n must be at least 1")
+    for q in qs:
+        if not 0.0 <= q <= 100.0:          # also refuses NaN
+            raise ValueError(f"percentile_targets: percentile {q} outside [0, 100]")
+    los, his, ts = [], [], []
+    for q in qs:
+        h = float(n - 1) * (q / 100.0)
+        lo = int(math.floor(h))
+        los.append(lo); his.append(min(lo + 1, n - 1)); ts.append(h - lo)
+    ranks = sorted(set(los) | {hi for hi, t in zip(his, ts) if t != 0.0})          # at t == 0 the upper value is not read: v[lo] stands in
+    pos = {r: i for i, r in enumerate(ranks)}
+    return ranks, [pos[lo] for lo in los], [pos[hi] if t != 0.0 else pos[lo] for lo, hi, t in zip(los, his, ts)], ts
+
+
+class StreamedGeneQuantiles:
+    """ops.gene_quantiles for a matrix that is only ever seen as a sequence of cell blocks: np.percentile(M_or_Z, qs, axis=cells) over
+    n_total cells, exact, with O(genes) memory (vcy_gene_select_*: an MSB-first radix select with 8-bit digits; 4 passes over f32 data,
+    8 over f64).  One pass = add_block() on EVERY block (any order, any blocking; the cells of all ranks in a cell-sharded run), then
+    advance(); when `done`, result() is the (len(qs), G) float64 tensor, bit for bit what gene_quantiles returns on the whole matrix.
+    two=True: the statistic of Z = M/scale_a + M2/scale_b (every add_block then takes M2 and the scales)."""
+
+    def __init__(self, G: int, qs: Sequence[float], n_total: int, dtype=None, device=None, two: bool = False):
+        self.G, self.n_total, self.two = int(G), int(n_total), bool(two)
+        self.ranks, self._lo, self._hi, self._t = percentile_targets(qs, self.n_total)
+        self.nq, self.nt = len(self._lo), len(self.ranks)
+        if self.nt > 16:
+            raise ValueError("StreamedGeneQuantiles: more than 16 distinct ranks")
+        self.dtype = resolve_dtype(dtype)
+        self.code = _DT[self.dtype]
+        self.dev = require_gpu() if device is None else torch.device(device)
+        L = _lib.lib()
+        self.passes = int(L.vcy_gene_select_passes(self.code))
+        self.state = torch.empty(int(L.vcy_gene_select_state_bytes(self.G, self.nt)) // 4, dtype=torch.int32, device=self.dev)
+        # int32 (the counters are uint32 and never exceed n_total < 2^31): the type the ranks' histograms are summed in
+        self.hist = torch.empty((self.nt, self.G, 256), dtype=torch.int32, device=self.dev)
+        ranks = (ctypes.c_int64 * self.nt)(*self.ranks)
+        _lib.check(L.vcy_gene_select_begin(self.state.data_ptr(), self.hist.data_ptr(), ranks, self.nt, self.n_total, self.G, self.code,
+                                           _stream()), "gene_select_begin")
+        self.pass_no = 0
+        self._cells = 0          # cells this rank added in the current pass
+
+    @property
+    def done(self) -> bool:
+        return self.pass_no >= self.passes
+
+    @property
+    def state_bytes(self) -> int:
+        return self.state.numel() * 4 + self.hist.numel() * 4
+
+    def add_block(self, M: CellMatrix, M2: Optional[CellMatrix] = None, scale_a: Optional[torch.Tensor] = None,
+                  scale_b: Optional[torch.Tensor] = None) -> None:
+        if self.done:
+            raise RuntimeError("StreamedGeneQuantiles.add_block: every pass is done")
+        if M.G != self.G or (M2 is not None and (M2.G != self.G or M2.C != M.C or M2.ld != M.ld)):
+            raise ValueError(f"StreamedGeneQuantiles.add_block: a block of {M.G} genes for a select over {self.G} genes (or M2 of another shape)")
+        if M.dtype != self.dtype or (M2 is not None and M2.dtype != self.dtype):
+            raise ValueError(f"StreamedGeneQuantiles.add_block: block dtype {M.dtype}, select dtype {self.dtype}")
+        if (M2 is not None) != self.two or (scale_a is not None) != self.two or (scale_b is not None) != self.two:
+            raise ValueError("StreamedGeneQuantiles.add_block: M2, scale_a and scale_b go with two=True, and only with it")
+        if M.C == 0:
+            return
+        if self._cells + M.C > self.n_total:
+            raise ValueError(f"StreamedGeneQuantiles.add_block: more than n_total = {self.n_total} cells in one pass")
+        f64 = lambda t: None if t is None else t.to(device=self.dev, dtype=torch.float64).contiguous()
+        scale_a, scale_b = f64(scale_a), f64(scale_b)
+        if self.two and (scale_a.numel() != self.G or scale_b.numel() != self.G):
+            raise ValueError("StreamedGeneQuantiles.add_block: scale_a / scale_b must hold one value per gene")
+        _lib.check(_lib.lib().vcy_gene_select_count_block(M.t.data_ptr(), None if M2 is None else M2.t.data_ptr(), _p(scale_a), _p(scale_b),
+                                                          self.state.data_ptr(), self.hist.data_ptr(), self.pass_no, self.nt, M.C, self.G,
+                                                          M.ld, self.code, _stream()), "gene_select_count_block")
+        self._cells += M.C
+
+    def advance(self, group=None) -> None:
+        """Ends a pass: sums the integer histograms (and the cell counts) over the ranks, then fixes the next digit of every target."""
+        from . import distributed as D
+        if self.done:
+            raise RuntimeError("StreamedGeneQuantiles.advance: every pass is done")
+        cells = self._cells
+        if D.active():
+            cells = int(D.all_reduce_sum(torch.tensor([cells], dtype=torch.int64, device=self.dev), group).item())
+        if cells == 0:
+            raise RuntimeError("StreamedGeneQuantiles.advance: no block was added in this pass")
+        if cells != self.n_total:
+            raise ValueError(f"StreamedGeneQuantiles.advance: the pass saw {cells} cells, the select was set up for n_total = {self.n_total}")
+        D.all_reduce_sum(self.hist[:1] if self.pass_no == 0 else self.hist, group)      # pass 0 counts one histogram for all targets
+        _lib.check(_lib.lib().vcy_gene_select_advance(self.state.data_ptr(), self.hist.data_ptr(), self.pass_no, self.nt, self.G, self.code,
+                                                      _stream()), "gene_select_advance")
+        self.pass_no += 1
+        self._cells = 0
+
+    def result(self) -> torch.Tensor:
+        if not self.done:
+            raise RuntimeError(f"StreamedGeneQuantiles.result: {self.pass_no} of {self.passes} passes done")
+        out = torch.empty((self.nq, self.G), dtype=torch.float64, device=self.dev)
+        lo, hi, t = (ctypes.c_int * self.nq)(*self._lo), (ctypes.c_int * self.nq)(*self._hi), (ctypes.c_double * self.nq)(*self._t)
+        _lib.check(_lib.lib().vcy_gene_select_finish(self.state.data_ptr(), lo, hi, t, self.nq, self.nt, out.data_ptr(), self.G, self.code,
+                                                     _stream()), "gene_select_finish")
+        return out
 
 
 def fit_weighted(Y: CellMatrix, X: CellMatrix, weight_mode: int, W: Optional[CellMatrix] = None, M: Optional[CellMatrix] = None,
