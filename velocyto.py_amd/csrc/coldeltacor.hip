@@ -191,6 +191,7 @@ template <> __device__ __forceinline__ float xform_s<float, VCY_LOG10, VCY_RULES
 
 template <typename T> __device__ __forceinline__ T pearson_from_moments(double sA, double sAA, double sAb, double sb, double sbb, double n)
 {
+    if (n < 2.0) return (T)__builtin_nan("");   // one gene: 0 / 0 in the reference's centred sums; f32 raw moments leave fl(a a) - a a != 0 there, an infinity
     const double cov = sAb - sA * sb / n;
     const double va = sAA - sA * sA / n;
     const double vb = sbb - sb * sb / n;
@@ -397,6 +398,18 @@ template <typename T> __host__ __device__ inline size_t grouped_lds_bytes(int gc
            8 * (size_t)(maxpairs + 2 > 64 + 4 * gc ? maxpairs + 2 : 64 + 4 * gc) + (size_t)(gc + 18) * sizeof(int) + 16;
 }
 
+// K lane-vectors of a chunk are evaluated; full: the chunk is a whole one (K == NV, rows loaded without predicates)
+template <int K, bool FULL> struct RowVecs { static constexpr int value = K; static constexpr bool full = FULL; };
+// f(RowVecs<k, false>) for the even k in [K, NV] that equals n
+template <int K, int NV, typename F> __device__ __forceinline__ void for_even_count(int n, F &f)
+{
+    if constexpr (K + 2 <= NV) {
+        if (n == K) f(RowVecs<K, false>{});
+        else for_even_count<K + 2, NV>(n, f);
+    } else
+        f(RowVecs<K, false>{});
+}
+
 template <typename T, int TR, int RULES, int GC, int NV, bool DUAL>
 __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restrict__ e, const T *__restrict__ d, const T *__restrict__ d2,
                                                                const int32_t *__restrict__ ixs, T *__restrict__ out, T *__restrict__ out2,
@@ -518,6 +531,9 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
         const int gl = min(GCHUNK, G - g0);
         const int nvec = (gl + N - 1) / N;                       // last vector may be partial: rows are zero-padded to ld
         const bool ragged = (gl % N) != 0;
+        // lane-vectors of this chunk that the row loop evaluates: all NV of a full chunk; in a short last chunk those that hold data,
+        // rounded up to the RD = 2 operand buffers of eval_row (wave-uniform: the scalar unit counts and branches on it)
+        const int nvu = min(NV, ((nvec + 63) / 64 + 1) & ~1);
         __syncthreads();
         if (tid == 0) *s_next = 0;
         if (sh < snh && sm < gcount) {
@@ -554,8 +570,8 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
                 }
             }
         }
-        if (gl < GCHUNK && sh < snh && sm < gcount)             // short last chunk: the lanes beyond it see zeros (f(0 - 0) adds nothing)
-            for (int v = nvec + sh * 64 + lane; v < NV * 64; v += 64 * snh) {
+        if (gl < GCHUNK && sh < snh && sm < gcount)             // short last chunk: the lanes beyond it, up to the last vector that is read, see zeros (f(0 - 0) adds nothing)
+            for (int v = nvec + sh * 64 + lane; v < nvu * 64; v += 64 * snh) {
                 reinterpret_cast<V *>(ec + sm * GCHUNK)[v] = V{};
                 reinterpret_cast<V *>(dc + sm * GCHUNK)[v] = V{};
                 if (DUAL) reinterpret_cast<V *>(dc2 + sm * GCHUNK)[v] = V{};
@@ -573,22 +589,25 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
 #define VCY_FENCE() __builtin_amdgcn_sched_barrier(0)
         // (a full chunk - every chunk but the last - loads its rows without predicates: the guarded form costs a v_cmp + s_and_saveexec +
         //  branch per vector, and in the f64 dual kernel the eight lane offsets it keeps for the compares were spilled and each reload
-        //  put an s_waitcnt vmcnt(0) in front of the next row load; the two forms are two instances of the row loop below)
-        auto load_row = [&](auto fullc, V (&x)[NV], unsigned long long dsc) {
+        //  put an s_waitcnt vmcnt(0) in front of the next row load; the two forms are separate instances of the row loop below, the guarded
+        //  one once per even number of vectors a short chunk can hold)
+        auto load_row = [&](auto nvc, V (&x)[NV], unsigned long long dsc) {
+            constexpr int KV = decltype(nvc)::value;            // vectors loaded: NV, or fewer in a short last chunk (which has its own instance for NV, too)
             const T *row = e + (int64_t)(dsc >> 19) * ld + g0;
 #pragma unroll
-            for (int u = 0; u < NV; ++u) {
+            for (int u = 0; u < KV; ++u) {
                 const int v = lane + 64 * u;
-                if (decltype(fullc)::value || v < nvec) x[u] = reinterpret_cast<const V *>(row)[v];
-                else x[u] = V{};                                 // short last chunk: zeros against the zeros staged below
+                if (decltype(nvc)::full || v < nvec) x[u] = reinterpret_cast<const V *>(row)[v];
+                else x[u] = V{};                                 // short last chunk: zeros against the zeros staged above
             }
         };
-        auto eval_row = [&](const V (&x)[NV], unsigned long long dsc) {
+        auto eval_row = [&](auto nvc, const V (&x)[NV], unsigned long long dsc) {
+            constexpr int KV = decltype(nvc)::value;            // vectors evaluated: NV, or fewer in a short last chunk
             int p = (int)(dsc & 2047);
             unsigned mask = (unsigned)(dsc >> 11) & 255u;
             int m = __builtin_ctz(mask);
             constexpr int RD = 2;       // operand buffers: RD - 1 vectors are in flight ahead of the arithmetic (3 buffers: 77.2 vs 76.8 ms, no gain)
-            static_assert(NV % RD == 0, "operand buffers rotate");
+            static_assert(KV % RD == 0, "operand buffers rotate");
             V eR[RD], bR[RD], b2R[RD];
             auto rd = [&](V &ev, V &bv, V &b2v, int mm, int u) {
                 ev = reinterpret_cast<const V *>(ec + mm * GCHUNK)[lane + 64 * u];
@@ -631,11 +650,11 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
                     }
                 };
 #pragma unroll
-                for (int u = 0; u < NV; ++u) {                  // vector u sits in buffer u % RD; the read of vector u + RD - 1 (of the next
+                for (int u = 0; u < KV; ++u) {                  // vector u sits in buffer u % RD; the read of vector u + RD - 1 (of the next
                     constexpr int AHEAD = RD - 1;                //  pair past the end of this one) is issued before vector u is folded
                     const int un = u + AHEAD;
-                    if (un < NV) rd(eR[un % RD], bR[un % RD], b2R[un % RD], m, un);
-                    else rd(eR[un % RD], bR[un % RD], b2R[un % RD], mn, un - NV);
+                    if (un < KV) rd(eR[un % RD], bR[un % RD], b2R[un % RD], m, un);
+                    else rd(eR[un % RD], bR[un % RD], b2R[un % RD], mn, un - KV);
                     VCY_FENCE();
                     fold(x[u], eR[u % RD], bR[u % RD], b2R[u % RD], u == 0);
                     VCY_FENCE();
@@ -657,7 +676,7 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
         // tickets: quads of rows first, then - for the last TAIL rows of the chunk - pairs: the waves reach the chunk barrier within one
         // ticket of each other, and a pair is half the wait of a quad (round 5, one box, stage D at 50k x 30k: f64 234.7 -> 233.8 ms,
         // f32 72.7 -> 71.7; profiles/r05_tail_tickets.txt)
-        auto rows = [&](auto fullc) {
+        auto rows = [&](auto nvc) {
             auto ticket = [&]() { int t = 0; if (lane == 0) t = atomicAdd(s_next, 1); return t; };     // lane 0 holds the value
             auto uni = [&](unsigned long long v) {
                 const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
@@ -672,39 +691,43 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
             int q = min(first_row(v), U);
             unsigned long long w0 = 0, w1 = 0, w2 = 0, w3 = 0;
             if (q < U) { w0 = uni(desc[q]); w1 = uni(desc[min(q + 1, U - 1)]); w2 = uni(desc[min(q + 2, U - 1)]); w3 = uni(desc[min(q + 3, U - 1)]); }
-            if (q < U) load_row(fullc, xa, w0);
+            if (q < U) load_row(nvc, xa, w0);
             while (v < T4) {                                     // a quad: rows q .. q + 3, all below U4
                 const int tv = ticket();
-                load_row(fullc, xb, w1);
-                eval_row(xa, w0);
-                load_row(fullc, xa, w2);
-                eval_row(xb, w1);
+                load_row(nvc, xb, w1);
+                eval_row(nvc, xa, w0);
+                load_row(nvc, xa, w2);
+                eval_row(nvc, xb, w1);
                 const int vn = __builtin_amdgcn_readfirstlane(tv);
                 const int qn = min(first_row(vn), U);
                 unsigned long long n0 = 0, n1 = 0, n2 = 0, n3 = 0;
                 if (qn < U) { n0 = desc[qn]; n1 = desc[min(qn + 1, U - 1)]; n2 = desc[min(qn + 2, U - 1)]; n3 = desc[min(qn + 3, U - 1)]; }
-                load_row(fullc, xb, w3);
-                eval_row(xa, w2);
+                load_row(nvc, xb, w3);
+                eval_row(nvc, xa, w2);
                 if (qn < U) { n0 = uni(n0); n1 = uni(n1); n2 = uni(n2); n3 = uni(n3); }
-                if (qn < U) load_row(fullc, xa, n0);
-                eval_row(xb, w3);
+                if (qn < U) load_row(nvc, xa, n0);
+                eval_row(nvc, xb, w3);
                 v = vn; q = qn; w0 = n0; w1 = n1; w2 = n2; w3 = n3;
             }
             while (q < U) {                                      // a pair: rows q, q + 1
                 const int tv = ticket();
                 const bool two = q + 1 < U;
-                if (two) load_row(fullc, xb, w1);
-                eval_row(xa, w0);
+                if (two) load_row(nvc, xb, w1);
+                eval_row(nvc, xa, w0);
                 const int vn = __builtin_amdgcn_readfirstlane(tv);
                 const int qn = min(first_row(vn), U);
                 unsigned long long n0 = 0, n1 = 0;
                 if (qn < U) { n0 = uni(desc[qn]); n1 = uni(desc[min(qn + 1, U - 1)]); }
-                if (qn < U) load_row(fullc, xa, n0);
-                if (two) eval_row(xb, w1);
+                if (qn < U) load_row(nvc, xa, n0);
+                if (two) eval_row(nvc, xb, w1);
                 v = vn; q = qn; w0 = n0; w1 = n1;
             }
         };
-        if (nvec == 64 * NV) rows(std::true_type{}); else rows(std::false_type{});
+        // a short last chunk evaluates the nvu vectors that hold data, not NV: one instance of the row loop per even count, chosen here by
+        // the scalar unit (nvu is the same in every wave), so that the loops inside keep compile-time bounds and the full-chunk instance
+        // is the code it was
+        if (nvec == 64 * NV) rows(RowVecs<NV, true>{});
+        else for_even_count<2, NV>(nvu, rows);
     }
     psb = wave_sum(psb); psbb = wave_sum(psbb);
     if (DUAL) { psb2 = wave_sum(psb2); psbb2 = wave_sum(psbb2); }
@@ -857,17 +880,34 @@ static int launch_grouped(const void *e, const void *d, const void *d2, const in
     // One workgroup per CU is resident (LDS), every group costs the same, so the last round of a launch would leave
     // most CUs idle for a whole group time (6250 groups on 256 CUs: 24.4 rounds; a 6250-cell shard of an 8-GPU run:
     // 3.05 rounds -> 4).  The groups beyond the last full round therefore run as the last blocks of the launch with their
-    // neighbour lists cut into narrower tiles, as many (group, tile) blocks as there are CUs.
+    // neighbour lists cut into narrower tiles: each base tile into s pieces, s chosen below.
     const int64_t groups = (C_out + GC - 1) / GC, W = dev.cus > 0 ? dev.cus : 256;
     const int64_t full = groups >= W ? groups / W * W : 0;       // (from one round on: a 270-group launch is one round + a tiled tail, not two rounds)
     const int64_t c_main = full * GC, c_tail = C_out - c_main;
     int64_t tw = tile;
     if (c_tail > 0) {
         const int64_t left = groups - full;
-        int64_t split = W / (left * ntiles);                       // how many pieces each base tile can be cut into
-        if (split < 1) split = 1;
-        tw = (tile + split - 1) / split;
-        if (tw < 16) tw = tile < 16 ? tile : 16;
+        // s minimises the modelled finish time of the tail, in units of a whole-width block: rounds of blocks on W CUs times (width of a
+        // piece + OVH), pieces no narrower than 16 columns, the smallest s among values within 2 % of each other.  OVH is what a round of
+        // narrow blocks costs besides its share of the pairs (staging, the key sort, rows shared by fewer pairs, the ragged end of a short
+        // row list at the chunk barrier), fitted to launches with s forced (profiles/stage_d_tail_split.txt; f64 / f32 stage D alone, ms):
+        //   50 000 cells, 142 / 106 groups left:  s = 1 186.9 / 69.7, 2 188.0 / 68.8, 3 186.1 / 68.9, 5 185.8 / 68.9, 7 185.4 / 68.9,
+        //                                         9 186.3 / 68.7, 14 186.5 / 69.0 - from 4 to 8 rounds of pieces of the same total width
+        //                                         f64 loses 1.1 ms of a 5.66 ms round (0.05 per round), f32 with OVH = 0 took s = 12, 69.1;
+        //   6 250 cells (a shard), 18 / 14 left:  s = 1 27.9 / 11.1, 3 25.6 / 9.8, 5 24.1 / 9.2, 9 23.5 / 8.8, 14 23.7 / 8.7 - one round
+        //                                         whatever s is, the narrowest pieces win or tie.
+        // The gain at 50 000 cells is far below the group time a lockstep model gives (1.1 of 5.7 ms in f64): the blocks of the last
+        // full round do not end together, so whole-width tail blocks already start on the CUs that finish first.
+        // The rule takes s = 5 / 2 at 50 000 cells and 14 / 16 on the shard (the rule before: 1 / 2 and 14 / 16).
+        constexpr double OVH = 0.05;
+        double best = 0.0;
+        int64_t bs = 1;
+        for (int64_t s = 1; s == 1 || (tile + s - 1) / s >= 16; ++s) {
+            const int64_t w = (tile + s - 1) / s, nt = (nrndm + w - 1) / w;
+            const double t = (double)((left * nt + W - 1) / W) * ((double)w / (double)tile + OVH);
+            if (s == 1 || t < 0.98 * best) { best = t; bs = s; }
+        }
+        tw = (tile + bs - 1) / bs;
     }
     auto nblocks = [&](int64_t ncell, int64_t w) { return ncell > 0 ? ((ncell + GC - 1) / GC + 7) / 8 * 8 * ((nrndm + w - 1) / w) : (int64_t)0; };
     hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks(c_main, tile) + nblocks(c_tail, tw))), dim3(1024), lds_g, st, (const T *)e, (const T *)d,
