@@ -490,6 +490,16 @@ int vcy_embedding_scaling_max_neighbors(void);
 int vcy_embedding_scaling(const void *hi_dim, const void *delta_S, const void *delta_S_rndm, const int32_t *ixs, const void *wdiff,
                           const void *wdiff_rndm, const int32_t *order, double *cos_proj, double *cos_proj_rndm, int64_t C, int64_t G,
                           int64_t ld, int64_t C_out, int64_t n, int dtype, vcy_stream stream);
+/* The same expression scaling (analysis.py:1714-1719) without a materialised delta_S: the fold forms it from the velocity chain's
+ * inputs, as vcy_coldeltacor_partial_fused forms d,
+ *   delta_S[c, g] = dt_shift * (Ux_sz[c, g] - (gamma[g] * hi_dim[c, g] + q[g]))            (analysis.py:1346, 1369, 1399)
+ * with the operations, order and casts of vcy_velocity_chain under the "constant_velocity" assumption without an eps threshold: cos_proj equals
+ * vcy_embedding_scaling on that chain's delta_S bit for bit.  hi_dim = Sx_sz: (C, ld), the cells themselves its first C_out rows;
+ * Ux_sz: at least C_out rows of the same ld; gamma, q: float32 (G), q may be NULL.  No randomised control.  Everything else -
+ * ixs, wdiff, order, cos_proj, the argument checks and VCY_ERR_UNSUPPORTED for n > vcy_embedding_scaling_max_neighbors() - as above. */
+int vcy_embedding_scaling_fused(const void *hi_dim, const void *Ux_sz, const float *gamma, const float *q, const int32_t *ixs, const void *wdiff,
+                                const int32_t *order, double *cos_proj, int64_t C, int64_t G, int64_t ld, int64_t C_out, int64_t n,
+                                double dt_shift, int dtype, vcy_stream stream);
 
 /* ---------------------------------------------------------------- stage F: prepare_markov
  * VelocytoLoom.prepare_markov (analysis.py:1818-1863) with cells_ixs=None: dense (n, n) Markov

@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import logging
 import warnings
-from typing import Any, Dict, List, Optional, Tuple, Union
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -740,26 +740,10 @@ class VelocytoLoom(PreprocessMixin):
         if not hasattr(self, f"delta_{embed}"):
             raise KeyError("This embedding does not have a delta_*")
         delta_embedding = np.asarray(getattr(self, f"delta_{embed}"))
-        grs = []
-        for dim_i in range(embedding.shape[1]):
-            m, M = np.min(embedding[:, dim_i]), np.max(embedding[:, dim_i])
-            m = m - 0.025 * np.abs(M - m)
-            M = M + 0.025 * np.abs(M - m)                      # (uses the widened m, as the reference does)
-            grs.append(np.linspace(m, M, steps[dim_i]))
-        gridpoints_coordinates = np.vstack([i.flat for i in np.meshgrid(*grs)]).T
-        neighs, dists = ops.knn_query(embedding, gridpoints_coordinates, n_neighbors)
-        neighs, dists = neighs.cpu().numpy().astype(np.int64), dists.cpu().numpy()
-        std = np.mean([(g[1] - g[0]) for g in grs])
-        scale = smooth * std
-        gaussian_w = np.exp(-0.5 * (dists / scale) ** 2) / (scale * np.sqrt(2 * np.pi))     # scipy.stats.norm.pdf
-        self.total_p_mass = gaussian_w.sum(1)
-        UZ = (delta_embedding[neighs] * gaussian_w[:, :, None]).sum(1) / np.maximum(1, self.total_p_mass)[:, None]
-        magnitude = np.linalg.norm(UZ, axis=1)
+        self.flow_grid, self.flow, self.flow_norm, self.flow_norm_magnitude, self.total_p_mass, neighs, gaussian_w = \
+            _grid_arrows(embedding, delta_embedding, smooth, steps, n_neighbors)
+        UZ = self.flow
         self.flow_embedding = embedding
-        self.flow_grid = gridpoints_coordinates
-        self.flow = UZ
-        self.flow_norm = UZ / np.percentile(magnitude, 99.5)
-        self.flow_norm_magnitude = np.linalg.norm(self.flow_norm, axis=1)
         if "_corr_random" in self.__dict__ and hasattr(self, f"delta_{embed}_random"):
             UZ_rndm = (np.asarray(getattr(self, f"delta_{embed}_random"))[neighs] * gaussian_w[:, :, None]).sum(1) / np.maximum(1, self.total_p_mass)[:, None]
             magnitude_rndm = np.linalg.norm(UZ, axis=1)        # (sic: the reference scales the control by the real magnitudes, :1812)
@@ -921,6 +905,48 @@ def fix_correlations(corr: torch.Tensor, corr_random: Optional[torch.Tensor], ne
             logging.warning(_NAN_WARNING.format(name))
 
 
+def _grid_arrows(embedding: np.ndarray, delta_embedding: np.ndarray, smooth: float, steps: Tuple, n_neighbors: int):
+    """grid_arrows plus what the randomised control's arrows reuse: the grid points' neighbours and their Gaussian weights."""
+    grs = []
+    for dim_i in range(embedding.shape[1]):
+        m, M = np.min(embedding[:, dim_i]), np.max(embedding[:, dim_i])
+        m = m - 0.025 * np.abs(M - m)
+        M = M + 0.025 * np.abs(M - m)                      # (uses the widened m, as the reference does)
+        grs.append(np.linspace(m, M, steps[dim_i]))
+    gridpoints_coordinates = np.vstack([i.flat for i in np.meshgrid(*grs)]).T
+    neighs, dists = ops.knn_query(embedding, gridpoints_coordinates, n_neighbors)
+    neighs, dists = neighs.cpu().numpy().astype(np.int64), dists.cpu().numpy()
+    std = np.mean([(g[1] - g[0]) for g in grs])
+    scale = smooth * std
+    gaussian_w = np.exp(-0.5 * (dists / scale) ** 2) / (scale * np.sqrt(2 * np.pi))     # scipy.stats.norm.pdf
+    total_p_mass = gaussian_w.sum(1)
+    UZ = (delta_embedding[neighs] * gaussian_w[:, :, None]).sum(1) / np.maximum(1, total_p_mass)[:, None]
+    magnitude = np.linalg.norm(UZ, axis=1)
+    flow_norm = UZ / np.percentile(magnitude, 99.5)
+    return gridpoints_coordinates, UZ, flow_norm, np.linalg.norm(flow_norm, axis=1), total_p_mass, neighs, gaussian_w
+
+
+def grid_arrows(embedding, delta_embedding, smooth: float = 0.5, steps: Tuple = (40, 40), n_neighbors: int = 100):
+    """calculate_grid_arrows (analysis.py:1735-1816) as a function of the embedding and its shift: the Gaussian-kernel average of
+    delta_embedding on a regular grid.  Returns (flow_grid, flow, flow_norm, flow_norm_magnitude, total_p_mass).  The neighbour search
+    of the grid points among the cells runs on the device (vcy_knn_query); the (grid x n_neighbors) weighting stays in NumPy."""
+    return _grid_arrows(np.asarray(embedding, dtype=np.float64), np.asarray(delta_embedding), smooth, steps, n_neighbors)[:5]
+
+
+def expression_cos(e: CellMatrix, dSs: Sequence, neigh_e: torch.Tensor, wdiffs: Sequence, order: Optional[torch.Tensor] = None) -> list:
+    """The two-step route of the expression scaling for lists wider than vcy_embedding_scaling sorts: estim = hi_dim @ (P - knn/n).T by
+    pooling (:1716; with the control's weights over the same gather, :1728), then the cosine projection of :1717 / :1729 against the
+    first C_out rows of each delta_S."""
+    C_out, n = (int(x) for x in neigh_e.shape)
+    indptr = torch.arange(0, (C_out + 1) * n, n, dtype=torch.int64, device=e.t.device)
+    if len(wdiffs) == 2:
+        estims = ops.knn_pool_w2(e, indptr, neigh_e.reshape(-1), wdiffs[0].reshape(-1), wdiffs[1].reshape(-1), C_out=C_out,
+                                 validate=False, order=order)
+    else:
+        estims = (ops.knn_pool(e, indptr, neigh_e.reshape(-1), wdiffs[0].reshape(-1), C_out=C_out, validate=False, order=order),)
+    return [ops.row_cosproj(m if m.C == C_out else CellMatrix(m.t[:C_out], m.G), est) for m, est in zip(dSs, estims)]      # :1717
+
+
 def embedding_shift(e: CellMatrix, dS: Optional[CellMatrix], dS_rndm: Optional[CellMatrix], neigh_e: torch.Tensor, neigh_emb: torch.Tensor,
                     corr: torch.Tensor, corr_rndm: Optional[torch.Tensor], embedding, sigma_corr: float, expression_scaling: bool,
                     scaling_penalty: float, cell0: int = 0, order: Optional[torch.Tensor] = None):
@@ -943,14 +969,7 @@ def embedding_shift(e: CellMatrix, dS: Optional[CellMatrix], dS_rndm: Optional[C
             cos = ops.embedding_scaling(e, dS, neigh_e, parts[0][1], dS_rndm if dual else None, parts[1][1] if dual else None, order=order,
                                         validate=False)
         if cos is None:
-            indptr = torch.arange(0, (C_out + 1) * n, n, dtype=torch.int64, device=e.t.device)
-            if dual:
-                estims = ops.knn_pool_w2(e, indptr, neigh_e.reshape(-1), parts[0][1].reshape(-1), parts[1][1].reshape(-1), C_out=C_out,
-                                         validate=False, order=order)
-            else:
-                estims = (ops.knn_pool(e, indptr, neigh_e.reshape(-1), parts[0][1].reshape(-1), C_out=C_out, validate=False, order=order),)
-            cos = [ops.row_cosproj(m if m.C == C_out else CellMatrix(m.t[:C_out], m.G), est) for m, est in zip(dSs, estims)]      # :1717
-            del estims
+            cos = expression_cos(e, dSs, neigh_e, [p[1] for p in parts], order)
         scalings = [torch.clamp(c / scaling_penalty, 0, 1) for c in cos]                                   # NaN stays NaN, like np.clip
     return [(tp, de if sc is None else de * sc[:, None], sc) for (tp, _, de), sc in zip(parts, scalings)]
 

@@ -83,11 +83,15 @@ class AtlasPath:
     def __init__(self, cS: ops.CsrCounts, cU: ops.CsrCounts, fS: torch.Tensor, fU: torch.Tensor, pcs: torch.Tensor, embedding: torch.Tensor, *,
                  c0: int = 0, C_total: Optional[int] = None, k: int = 30, n_neighbors: int = 500, sampled_fraction: float = 0.5,
                  sampling_probs=(0.5, 0.1), block_cells: int = 0, dtype=torch.float32, psc: float = 1e-10, seed: int = 15071990,
-                 knn: str = "auto", fit: str = "slope"):
+                 knn: str = "auto", fit: str = "slope", shift: bool = False, sigma_corr: float = 0.05, expression_scaling: bool = True,
+                 scaling_penalty: float = 1.0):
         """fit: how stage B fits gamma.  "slope" (the default): gamma = max(0, sum xy / sum xx), unweighted, no offset (fit_slope,
         estimation.py:267-279).  "maxmin_diag" (or "default"): velocyto's default fit_gammas(weights="maxmin_diag", fit_offset=True)
         (analysis.py:1179-1257), the recipe of VelocytoLoom.fit_gammas and ShardedLoom.fit_gammas, with the per-gene percentiles
-        taken by a streamed exact select (ops.StreamedGeneQuantiles): 9 walks over the pooled blocks in f32, 17 in f64."""
+        taken by a streamed exact select (ops.StreamedGeneQuantiles): 9 walks over the pooled blocks in f32, 17 in f64.
+        shift: also calculate_embedding_shift (analysis.py:1670-1733, stage E) with sigma_corr, expression_scaling and scaling_penalty
+        as there, block by block while the block is in the staging buffers: run() then leaves tp, delta_embedding, scaling and
+        delta_embedding_unscaled of the rank's own cells (see _stage_e); delta_S is never formed."""
         if fit not in ("slope", "maxmin_diag", "default"):
             raise ValueError(f"AtlasPath: unknown fit={fit!r} (\"slope\", \"maxmin_diag\" or \"default\")")
         self.fit = "slope" if fit == "slope" else "maxmin_diag"
@@ -119,6 +123,9 @@ class AtlasPath:
         self.neigh = sample_neighbors(emb_full, self.c0, self.c1, n_neighbors, sampled_fraction, sampling_probs, seed)
         self.nrndm = int(self.neigh.shape[1])
         self._pcs_full = pcs_full
+        self.shift, self.sigma_corr = bool(shift), float(sigma_corr)
+        self.expression_scaling, self.scaling_penalty = bool(expression_scaling), float(scaling_penalty)
+        self._emb_full = emb_full if self.shift else None       # stage E reads the neighbours' coordinates (C x 2 doubles: 16 MB at 1M cells)
         del emb_full
         # ---- E rows: the rows of e = Sx_sz this rank reads = own cells + sampled neighbours owned elsewhere (e_out, ascending)
         need_e = torch.zeros(self.C, dtype=torch.bool, device=dev)
@@ -157,6 +164,15 @@ class AtlasPath:
         self.select_state_bytes = 0        # ... and the bytes the streamed select held at its peak
         self._in_buf = None                # the block whose own rows the staging buffers hold
         self.stage_ms = np.zeros(4)
+        self.stage_e_ms = 0.0              # shift=True, run(timed=True): milliseconds of stage E (kept out of stage_ms)
+        self.tp = self.delta_embedding = self.delta_embedding_unscaled = self.scaling = None
+        if self.shift:
+            edim = int(self._emb_full.shape[1])
+            self.tp = torch.empty((self.nloc, self.nrndm), dtype=self.dtype, device=dev)
+            self.delta_embedding = torch.empty((self.nloc, edim), dtype=torch.float64, device=dev)
+            self.delta_embedding_unscaled = torch.empty((self.nloc, edim), dtype=torch.float64, device=dev)
+            if self.expression_scaling:
+                self.scaling = torch.empty(self.nloc, dtype=torch.float64, device=dev)
         self._resident = None
         self._plan = None
         self.peak_block_bytes = 0
@@ -329,16 +345,46 @@ class AtlasPath:
             tms[1] += ev[0].elapsed_time(ev[1])
         return gamma, q
 
+    # ------------------------------------------------------------------ stage E of one block
+    def _stage_e(self, b0: int, b1: int, e_buf: ops.CellMatrix, Ux_b: ops.CellMatrix, gamma: torch.Tensor, q: Optional[torch.Tensor],
+                 ixs: torch.Tensor) -> None:
+        """calculate_embedding_shift (analysis.py:1670-1733) for the block b0..b1-1 whose correlation rows were just written, while
+        e_buf = [block | outside rows] and Ux_b still hold it: transition probabilities and the unscaled shift from the NaN -> 1 copy of
+        the rows (:1604-1607; self.corr keeps its NaNs) with the GLOBAL neighbour numbers, the expression scaling from the block's
+        local lists with delta_S formed in the kernel's fold (vcy_embedding_scaling_fused)."""
+        nb = b1 - b0
+        neigh = self.neigh[b0:b1]
+        fixed = self.corr[b0:b1].clone()
+        ops.corr_fixup(fixed, neigh, cell0=self.c0 + b0, zero_self=True, fix_nan=True, nan_to=1.0)
+        tp, wd, de = ops.transition_prob(fixed, neigh, self._emb_full, self.sigma_corr, cell0=self.c0 + b0)
+        self.tp[b0:b1] = tp
+        self.delta_embedding_unscaled[b0:b1] = de
+        if not self.expression_scaling:
+            self.delta_embedding[b0:b1] = de
+            return
+        cos = ops.embedding_scaling_fused(e_buf, Ux_b, gamma, q, ixs, wd, validate=False)
+        if cos is None:
+            # lists wider than the kernel sorts: the block's delta_S is materialised after all and takes embedding_shift's two-step route
+            from .analysis import expression_cos
+            dS = ops.velocity_chain(e_buf.rows(0, nb), Ux_b, gamma, q, want=("delta_S",))["delta_S"]
+            cos = expression_cos(e_buf, [dS], ixs, [wd])
+            del dS
+        sc = torch.clamp(cos[0] / self.scaling_penalty, 0, 1)                              # NaN stays NaN, like np.clip
+        self.scaling[b0:b1] = sc
+        self.delta_embedding[b0:b1] = de * sc[:, None]
+
     def run(self, timed: bool = False) -> torch.Tensor:
         """One pass of the path; returns the rank's correlation rows.  timed=True adds the stages' milliseconds to stage_ms =
         [A pooling, B fit, A kNN search, D].  With fit="maxmin_diag" stage B includes everything its extra walks over the data
-        cost, the re-pooling of the blocks in streamed mode too; only the first walk's pooling counts as stage A."""
+        cost, the re-pooling of the blocks in streamed mode too; only the first walk's pooling counts as stage A.  shift=True: stage E
+        of every block follows its stage D (results in tp, delta_embedding, scaling, delta_embedding_unscaled); its milliseconds go to
+        stage_e_ms."""
         dev, G = self.dev, self.G
         if self._plan is None:
             self._plan_blocks()
         single = len(self._plan) == 1
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        tA = tB = tD = tK = 0.0
+        tA = tB = tD = tK = tE = 0.0
         # ---- A, first half: the exact kNN search of the own cells among all cells (analysis.py:1005).  The graph of a dataset
         #      does not change between passes - the count-row halo was built from it - but the search is part of
         #      knn_imputation and of the metric, so every pass repeats it
@@ -399,18 +445,39 @@ class AtlasPath:
             ops.coldeltacor_partial_fused(e_buf, Ux_b, gamma, q, ixs, ops.SQRT, self.rules, self.psc, cell0=0, u_row0=0,
                                           out=self.corr[b0:b1], validate=False)
             ev[2].record()
+            if self.shift:
+                self._stage_e(b0, b1, e_buf, Ux_b, gamma, q, ixs)
+                ev[3].record()
             if timed:
                 torch.cuda.synchronize()
                 tA += ev[0].elapsed_time(ev[1]); tD += ev[1].elapsed_time(ev[2])
+                if self.shift:
+                    tE += ev[2].elapsed_time(ev[3])
         if single:
             self._resident = (self._ebuf, self._ubuf)
         if timed:
             self.stage_ms += np.array([tA, tB, tK, tD])
+            self.stage_e_ms += tE
         return self.corr
 
     def gathered_corr(self) -> torch.Tensor:
         """All cells' correlation rows on every rank (the RCCL all-gather north_star names)."""
         return D.all_gather_rows(self.corr, self.C)
+
+    def gathered_shift(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """All cells' (delta_embedding, scaling) on every rank after a run with shift=True; scaling is None without expression_scaling."""
+        assert self.shift, "AtlasPath(shift=True) computes the embedding shift"
+        return (D.all_gather_rows(self.delta_embedding, self.C),
+                None if self.scaling is None else D.all_gather_rows(self.scaling, self.C))
+
+
+def grid_arrows(embedding, delta_embedding, smooth: float = 0.5, steps: Tuple = (40, 40), n_neighbors: int = 100):
+    """calculate_grid_arrows (analysis.py:1735-1816) on gathered atlas results - the embedding of all cells and
+    AtlasPath.gathered_shift()[0]: (flow_grid, flow, flow_norm, flow_norm_magnitude, total_p_mass) of analysis.grid_arrows; 40 x 40
+    arrows are what one draws for a million cells."""
+    from .analysis import grid_arrows as _grid_arrows
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return _grid_arrows(to_np(embedding), to_np(delta_embedding), smooth, steps, n_neighbors)
 
 
 def memory_plan(C: int, G: int, nnz_per_cell: float, world: int, block_cells: int, nrndm: int = 250, k: int = 30, count_bytes: int = 1,

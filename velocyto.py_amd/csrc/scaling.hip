@@ -47,12 +47,18 @@ template <typename T> __host__ __device__ inline size_t scaling_lds_bytes(int np
 }
 
 // DUAL: a second weight set w2 / second matrix dS2 (the randomised control) over the same lists
-template <typename T, bool DUAL>
+// FUSED (never DUAL): delta_S is not read but formed in the fold from the velocity chain's inputs, as fused stage D forms d
+// (csrc/coldeltacor.hip: fused_dmat): `dS` is Ux_sz (at least C_out rows, same ld), a member's own Sx chunk is row s_cells[m] of `hi`,
+//     delta_S = dt_shift * (u - ((T)gamma[g] * s + (T)q[g]))                     (analysis.py:1346, 1369, 1399)
+// - the operations, order and casts of k_velocity_chain's delta_S: the result equals the unfused kernel on the materialised matrix bit for bit
+template <typename T, bool DUAL, bool FUSED = false>
 __global__ __launch_bounds__(64 * SC_WAVES, 4) void k_embedding_scaling(const T *__restrict__ hi, const T *__restrict__ dS, const T *__restrict__ dS2,
                                                                          const int32_t *__restrict__ ixs, const T *__restrict__ w, const T *__restrict__ w2,
                                                                          const int32_t *__restrict__ order, double *__restrict__ cos1, double *__restrict__ cos2,
-                                                                         int G, int64_t ld, int C_out, int n, int npad)
+                                                                         int G, int64_t ld, int C_out, int n, int npad,
+                                                                         const float *__restrict__ gamma = nullptr, const float *__restrict__ q = nullptr, T dt_shift = T(1))
 {
+    static_assert(!(DUAL && FUSED), "the fused fold has no randomised control");
     using V = typename Vec<T>::type;
     constexpr int N = Vec<T>::N;
     constexpr bool BCAST = sizeof(T) == 8;                           // weights reach the f64 multiply-adds through DPP (fmac_bcast)
@@ -211,6 +217,15 @@ __global__ __launch_bounds__(64 * SC_WAVES, 4) void k_embedding_scaling(const T 
             }
         }
         // ---- fold the chunk into the member's sums: sum_g dS * estim, sum_g estim^2 (fp64), one transposing wave reduction per member
+        float gm[N], qq[N];                                           // FUSED: the chunk's gamma and q, loaded once for all members
+        if constexpr (FUSED) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                const int g = v * N + k;
+                gm[k] = (in && g < G) ? gamma[g] : 0.f;
+                qq[k] = (in && g < G && q) ? q[g] : 0.f;
+            }
+        }
 #pragma unroll
         for (int m = 0; m < SC_GC; ++m) {
             if (m < gcount) {
@@ -219,8 +234,21 @@ __global__ __launch_bounds__(64 * SC_WAVES, 4) void k_embedding_scaling(const T 
                     const int64_t ro = (int64_t)s_cells[m] * ld + voff;
                     const V a = *reinterpret_cast<const V *>(dS + ro);
                     const T *ap = reinterpret_cast<const T *>(&a);
+                    if constexpr (FUSED) {
+                        const V sv = *reinterpret_cast<const V *>(hi + ro);
+                        const T *sp = reinterpret_cast<const T *>(&sv);
 #pragma unroll
-                    for (int k = 0; k < N; ++k) { const double e = (double)acc[m][k]; n1 = fma((double)ap[k], e, n1); d1 = fma(e, e, d1); }
+                        for (int k = 0; k < N; ++k) {
+                            const T upred = (T)gm[k] * sp[k] + (T)qq[k];
+                            const T ds = dt_shift * (ap[k] - upred);
+                            const double e = (double)acc[m][k];
+                            n1 = fma((double)ds, e, n1);
+                            d1 = fma(e, e, d1);
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < N; ++k) { const double e = (double)acc[m][k]; n1 = fma((double)ap[k], e, n1); d1 = fma(e, e, d1); }
+                    }
                     if (DUAL) {
                         const V b = *reinterpret_cast<const V *>(dS2 + ro);
                         const T *bp = reinterpret_cast<const T *>(&b);
@@ -251,6 +279,37 @@ using namespace vcy;
 
 extern "C" int vcy_embedding_scaling_max_neighbors(void) { return SC_MAXN; }
 
+// one launch path for both entry points: `dS` is delta_S, or Ux_sz with gamma (the fused fold)
+static int scaling_launch(const char *what, const void *hi_dim, const void *dS, const void *dS2, const float *gamma, const float *q, double dt_shift,
+                          const int32_t *ixs, const void *w, const void *w2, const int32_t *order, double *cos1, double *cos2, int64_t C, int64_t G,
+                          int64_t ld, int64_t C_out, int64_t n, int dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(C > 0 && G > 0 && ld >= G && C_out > 0 && C_out <= C && n > 0, "embedding_scaling: bad shape");
+    VCY_REQUIRE(dtype == VCY_F32 || dtype == VCY_F64, "embedding_scaling: bad dtype");
+    VCY_REQUIRE(ld % (dtype == VCY_F32 ? 4 : 2) == 0 && ((uintptr_t)hi_dim % 16) == 0 && ((uintptr_t)dS % 16) == 0 && ((uintptr_t)dS2 % 16) == 0,
+                "embedding_scaling: rows must be 16-byte aligned");
+    if (n > SC_MAXN) return fail(VCY_ERR_UNSUPPORTED, "%s: neighbour lists wider than %lld are pooled with vcy_knn_pool_w2 + vcy_row_cosproj", what, (long long)SC_MAXN);
+    int npad = 2;
+    while (npad < SC_GC * n) npad <<= 1;
+    const int64_t ngroups = (C_out + SC_GC - 1) / SC_GC, blocks = (ngroups + 7) / 8 * 8;
+    hipStream_t st = as_stream(stream);
+    const bool dual = dS2 != nullptr, fused = gamma != nullptr;
+#define VCY_SCALING(T, D, F)                                                                                                               \
+    do {                                                                                                                                   \
+        const size_t lds = scaling_lds_bytes<T>(npad, (int)(SC_GC * n));                                                                  \
+        auto kern = k_embedding_scaling<T, D, F>;                                                                                          \
+        int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);                                                            \
+        if (rc) return rc;                                                                                                                 \
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * SC_WAVES), lds, st, (const T *)hi_dim, (const T *)dS, (const T *)dS2, ixs, \
+                           (const T *)w, (const T *)w2, order, cos1, cos2, (int)G, ld, (int)C_out, (int)n, npad, gamma, q, (T)dt_shift);   \
+    } while (0)
+    if (dtype == VCY_F32) { if (fused) VCY_SCALING(float, false, true); else if (dual) VCY_SCALING(float, true, false); else VCY_SCALING(float, false, false); }
+    else { if (fused) VCY_SCALING(double, false, true); else if (dual) VCY_SCALING(double, true, false); else VCY_SCALING(double, false, false); }
+#undef VCY_SCALING
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
 extern "C" int vcy_embedding_scaling(const void *hi_dim, const void *delta_S, const void *delta_S_rndm, const int32_t *ixs, const void *wdiff,
                                      const void *wdiff_rndm, const int32_t *order, double *cos_proj, double *cos_proj_rndm, int64_t C, int64_t G,
                                      int64_t ld, int64_t C_out, int64_t n, int dtype, vcy_stream stream)
@@ -258,28 +317,15 @@ extern "C" int vcy_embedding_scaling(const void *hi_dim, const void *delta_S, co
     VCY_REQUIRE(hi_dim && delta_S && ixs && wdiff && cos_proj, "embedding_scaling: null pointer");
     VCY_REQUIRE((delta_S_rndm == nullptr) == (wdiff_rndm == nullptr) && (delta_S_rndm == nullptr) == (cos_proj_rndm == nullptr),
                 "embedding_scaling: delta_S_rndm / wdiff_rndm / cos_proj_rndm go together");
-    VCY_REQUIRE(C > 0 && G > 0 && ld >= G && C_out > 0 && C_out <= C && n > 0, "embedding_scaling: bad shape");
-    VCY_REQUIRE(dtype == VCY_F32 || dtype == VCY_F64, "embedding_scaling: bad dtype");
-    VCY_REQUIRE(ld % (dtype == VCY_F32 ? 4 : 2) == 0 && ((uintptr_t)hi_dim % 16) == 0 && ((uintptr_t)delta_S % 16) == 0 && ((uintptr_t)delta_S_rndm % 16) == 0,
-                "embedding_scaling: rows must be 16-byte aligned");
-    if (n > SC_MAXN) return fail(VCY_ERR_UNSUPPORTED, "%s: neighbour lists wider than %lld are pooled with vcy_knn_pool_w2 + vcy_row_cosproj", "embedding_scaling", (long long)SC_MAXN);
-    int npad = 2;
-    while (npad < SC_GC * n) npad <<= 1;
-    const int64_t ngroups = (C_out + SC_GC - 1) / SC_GC, blocks = (ngroups + 7) / 8 * 8;
-    hipStream_t st = as_stream(stream);
-    const bool dual = delta_S_rndm != nullptr;
-#define VCY_SCALING(T, D)                                                                                                                  \
-    do {                                                                                                                                   \
-        const size_t lds = scaling_lds_bytes<T>(npad, (int)(SC_GC * n));                                                                  \
-        auto kern = k_embedding_scaling<T, D>;                                                                                             \
-        int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);                                                            \
-        if (rc) return rc;                                                                                                                 \
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * SC_WAVES), lds, st, (const T *)hi_dim, (const T *)delta_S, (const T *)delta_S_rndm, \
-                           ixs, (const T *)wdiff, (const T *)wdiff_rndm, order, cos_proj, cos_proj_rndm, (int)G, ld, (int)C_out, (int)n, npad); \
-    } while (0)
-    if (dtype == VCY_F32) { if (dual) VCY_SCALING(float, true); else VCY_SCALING(float, false); }
-    else { if (dual) VCY_SCALING(double, true); else VCY_SCALING(double, false); }
-#undef VCY_SCALING
-    VCY_LAUNCH_CHECK();
-    return VCY_OK;
+    return scaling_launch("embedding_scaling", hi_dim, delta_S, delta_S_rndm, nullptr, nullptr, 1.0, ixs, wdiff, wdiff_rndm, order, cos_proj, cos_proj_rndm,
+                          C, G, ld, C_out, n, dtype, stream);
+}
+
+extern "C" int vcy_embedding_scaling_fused(const void *hi_dim, const void *Ux_sz, const float *gamma, const float *q, const int32_t *ixs, const void *wdiff,
+                                           const int32_t *order, double *cos_proj, int64_t C, int64_t G, int64_t ld, int64_t C_out, int64_t n,
+                                           double dt_shift, int dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(hi_dim && Ux_sz && gamma && ixs && wdiff && cos_proj, "embedding_scaling_fused: null pointer");
+    return scaling_launch("embedding_scaling_fused", hi_dim, Ux_sz, nullptr, gamma, q, dt_shift, ixs, wdiff, nullptr, order, cos_proj, nullptr,
+                          C, G, ld, C_out, n, dtype, stream);
 }

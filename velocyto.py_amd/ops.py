@@ -1866,6 +1866,34 @@ def embedding_scaling(hi: CellMatrix, dS: CellMatrix, ixs, wdiff: torch.Tensor, 
     return (cos, cos2) if dual else (cos,)
 
 
+def embedding_scaling_fused(hi: CellMatrix, Ux: CellMatrix, gamma: torch.Tensor, q: Optional[torch.Tensor], ixs, wdiff: torch.Tensor,
+                            dt_shift: float = 1.0, order: Optional[torch.Tensor] = None, validate: bool = True):
+    """embedding_scaling without a materialised delta_S (vcy_embedding_scaling_fused): the fold forms delta_S = dt_shift * (Ux - (gamma * hi + q))
+    from the velocity chain's inputs, bit-identical to velocity_chain(want=("delta_S",)) + embedding_scaling.  hi = Sx_sz, the cells
+    themselves its first C_out rows; Ux: at least C_out rows of the same width.  Returns (cos_proj,) fp64, or None for lists wider than
+    the kernel sorts and for empty input - the caller then materialises delta_S and pools with knn_pool + row_cosproj."""
+    dev = hi.t.device
+    ix = _as_i32(ixs, dev)
+    C_out, n = ix.shape
+    L = _lib.lib()
+    if n > int(L.vcy_embedding_scaling_max_neighbors()) or n == 0 or C_out == 0:
+        return None
+    assert Ux.dtype == hi.dtype and Ux.ld == hi.ld and Ux.G == hi.G and C_out <= Ux.C and C_out <= hi.C
+    if validate and (int(ix.min()) < 0 or int(ix.max()) >= hi.C):
+        raise ValueError("neighbour index out of range")
+    w = wdiff.to(device=dev, dtype=hi.dtype).contiguous()
+    assert tuple(w.shape) == (C_out, n)
+    gamma = gamma.to(device=dev, dtype=torch.float32).contiguous()
+    q = None if q is None else q.to(device=dev, dtype=torch.float32).contiguous()
+    assert gamma.numel() == hi.G and (q is None or q.numel() == hi.G)
+    cos = torch.empty(C_out, dtype=torch.float64, device=dev)
+    order, n_sched = _schedule(order, dev, C_out)
+    assert n_sched == C_out, "embedding_scaling_fused: the schedule must cover every cell"
+    _lib.check(L.vcy_embedding_scaling_fused(hi.t.data_ptr(), Ux.t.data_ptr(), gamma.data_ptr(), _p(q), ix.data_ptr(), w.data_ptr(), _p(order),
+                                             cos.data_ptr(), hi.C, hi.G, hi.ld, C_out, n, float(dt_shift), hi.code, _stream()), "embedding_scaling_fused")
+    return (cos,)
+
+
 def _run_steps(step, x: torch.Tensor, y: torch.Tensor, n_steps: int) -> torch.Tensor:
     """n_steps of step(src, dst) ping-ponging between x and y; returns the buffer that holds the last iterate.  Long loops are
     launch-bound (a few tiny kernels per step, thousands of steps): an x -> y -> x pair of steps is captured into a hipGraph once
