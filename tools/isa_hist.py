@@ -1,6 +1,7 @@
 """Mnemonic histogram of the branch-free pair body of a stage-D kernel in a hipcc -S listing.
 usage: python tools/isa_hist.py file.s [kernel-name substring] [marker mnemonic, default v_sqrt_f32]
-The body is the basic block (between labels / branches) holding 24 marker instructions."""
+The body is the basic block (between labels / branches) holding 24 marker instructions; an s_cbranch_execz that only skips forward over
+masked-off lanes (the f64 zero rule as an execution mask) and the label it skips to do not end a block."""
 import collections
 import re
 import sys
@@ -11,19 +12,24 @@ marker = sys.argv[3] if len(sys.argv) > 3 else "v_sqrt_f32"
 lines = open(path).read().split("\n")
 start = next(i for i, l in enumerate(lines) if want in l and re.match(r"^_Z\S+:", l))
 end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
-blocks, cur = [], []
+blocks, cur, skips = [], [], set()
 for l in lines[start:end]:
     t = l.strip()
     if not t or t.startswith(";") or t.startswith("."):
         if t.startswith(".LBB"):
-            blocks.append(cur); cur = []
+            if t.split(":")[0] in skips:
+                skips.discard(t.split(":")[0])
+                continue
+            blocks.append(cur); cur = []; skips = set()
         continue
     if re.match(r"^\S+:(\s|$)", t):
         blocks.append(cur); cur = []
         continue
     cur.append(t.split()[0])
-    if t.startswith("s_cbranch") or t.startswith("s_branch"):
-        blocks.append(cur); cur = []
+    if t.startswith("s_cbranch_execz"):
+        skips.add(t.split()[1])
+    elif t.startswith("s_cbranch") or t.startswith("s_branch"):
+        blocks.append(cur); cur = []; skips = set()
 blocks.append(cur)
 for b in blocks:
     n = sum(1 for m in b if m.startswith(marker))

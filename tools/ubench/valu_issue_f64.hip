@@ -159,6 +159,46 @@ __global__ void __launch_bounds__(256) k_elem(double *out, unsigned long long *c
     out[blockIdx.x * 256 + threadIdx.x] = sA[0] + sA[1] + sAA[0] + sAA[1] + sAb[0] + sAb[1];
     if ((threadIdx.x & 63) == 0) cyc[blockIdx.x * 4 + (threadIdx.x >> 6)] = t1 - t0;
 }
+// round 8: the zero rule as an execution mask.  The compare comes first and switches the lane off for the rest of the element (root and the
+// three moment updates run under `if (!(|t| < 1e-16))`: v_cmp_nlt_f64 + s_and_saveexec_b64 + s_cbranch_execz + s_or_b64), the seed takes
+// (float)x directly: no v_cndmask, 15 vector instructions per element.  The same two interleaved partial sums per moment as k_elem<7>, so the
+// two compare like for like.  ABS2: sum A^2 taken as the sum of |t| + psc over the kept elements (a v_add_f64 for a v_fma_f64; no kept-count
+// is needed under the mask).  The data has no discarded element, like k_elem<7>'s: the mask is always full and the branch never taken.
+__device__ __forceinline__ double sqrt_seed1(double x)                     // sqrt_seedzero1 without the rule
+{
+    const float xf = (float)x;
+    const float yf = __builtin_amdgcn_rsqf(xf);
+    const double s0 = (double)(xf * yf), h = (double)(0.5f * yf);
+    const double d = fma(-s0, s0, x);
+    return fma(d, h, s0);
+}
+template <bool ABS2>
+__global__ void __launch_bounds__(256) k_elem_masked(double *out, unsigned long long *cyc, double seed)
+{
+    constexpr int NE = 4;
+    double x[NE], e[NE], b[NE], sA[2] = {0, 0}, sAA[2] = {0, 0}, sAb[2] = {0, 0};
+    for (int k = 0; k < NE; ++k) { x[k] = seed * (threadIdx.x + k + 1); e[k] = 0.37 * (k + 1); b[k] = 0.11 * (threadIdx.x + k); }
+    const double psc = seed * 1e-10;
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int i = 0; i < ITER * REP; ++i) {
+#pragma unroll
+        for (int k = 0; k < NE; ++k) {
+            const double t = x[k] - e[k];
+            if (!(fabs(t) < 1e-16)) {
+                const double a = copysign(sqrt_seed1(fabs(t) + psc), t);
+                sA[k & 1] += a;
+                sAA[k & 1] = ABS2 ? sAA[k & 1] + (fabs(t) + psc) : fma(a, a, sAA[k & 1]);
+                sAb[k & 1] = fma(a, b[k], sAb[k & 1]);
+            }
+            x[k] += 0.5;
+        }
+    }
+    asm volatile("s_nop 0" ::: "memory");
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    out[blockIdx.x * 256 + threadIdx.x] = sA[0] + sA[1] + sAA[0] + sAA[1] + sAb[0] + sAb[1];
+    if ((threadIdx.x & 63) == 0) cyc[blockIdx.x * 4 + (threadIdx.x >> 6)] = t1 - t0;
+}
+
 // accuracy of the candidates against the library square root over a sweep of magnitudes
 __global__ void k_sqrt_err(double *maxrel, int n)
 {
@@ -241,6 +281,8 @@ int main()
     run("f64 element, zero rule on the seed's argument (round 4, second step: the kernel's)", k_elem<5>, w, 4, "element");
     run("f64 element, the same with s0 = x y and h = y / 2 as f64 products (not kept)", k_elem<6>, w, 4, "element");
     run("f64 element, zero rule on the seed's argument, ONE Newton correction (round 7: VCY_RULES_PARTIAL)", k_elem<7>, w, 4, "element");
+    run("f64 element, zero rule as an execution mask, ONE Newton correction (round 8)", k_elem_masked<false>, w, 4, "element");
+    run("f64 element, the same with sum A^2 as sum (|t| + psc) over the kept elements (round 8)", k_elem_masked<true>, w, 4, "element");
     run("f64 element, library sqrt()", k_elem<3>, w, 4, "element");
     double *mr; hipMalloc(&mr, 48); hipMemset(mr, 0, 48);
     k_sqrt_err<<<1024, 256>>>(mr, 1 << 26);

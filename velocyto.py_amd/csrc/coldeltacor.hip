@@ -109,7 +109,8 @@ template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_
     return copysign(fma(d, h, s1), t);
 }
 
-// VCY_RULES_PARTIAL, the default f64 element: the same seed, zero rule and sign with ONE Newton correction - 16 instructions per element,
+// VCY_RULES_PARTIAL, the default f64 element: the same seed, zero rule and sign with ONE Newton correction - 16 instructions per element
+// (15 in the grouped kernel, where the zero rule is an execution mask: ZeroMasked<> / xform_kept below; this form serves k_cdc_partial),
 // the second `d = x - s1^2`, `s1 + d h` pair (two v_fma_f64) left out.  Error of the root after the one correction, relative: with e0 the
 // error of the 24-bit seed s0 (the rounding of x to f32, 2^-24, half of it reaching the root; v_rsq_f32, 1 ulp; the rounding of the f32 product
 // x_f y_f: e0 <= 1.75 2^-23), e_h that of h against 1 / (2 sqrt x) (v_rsq_f32 + half the conversion's: <= 1.25 2^-23),
@@ -151,6 +152,31 @@ template <> __device__ __forceinline__ float xform<float, VCY_SQRT, VCY_RULES_PA
 // variant has f(0) = -sqrt(psc) (t > 0 fails at 0): shifted too, so that identical cells give an exact zero variance
 // (NaN, like the reference's centred sums) instead of f32 rounding noise.  Partial sqrt and linear have f(0) = 0.
 template <int TR, int RULES> struct Shifted { static constexpr bool value = TR == VCY_LOG10 || (TR == VCY_SQRT && RULES == VCY_RULES_FULL); };   // f(0) != 0
+
+// Zero rule as an execution mask (the grouped kernel's f64 partial-sqrt elements only).  A discarded element (|t| < 1e-16) adds nothing to
+// sum A, sum A^2 or sum A b, so instead of selecting a zero root (v_cmp_f64 + v_cndmask_b32 on the seed's argument, then three moment updates
+// that add the zero) the compare switches the lane off for the rest of the element: v_cmp_nlt_f64 + s_and_saveexec_b64 [+ s_cbranch_execz] +
+// s_or_b64 - the select moves from the vector ALU to the scalar unit, 15 vector instructions per element instead of 16.  xform_kept is the
+// element of a lane that stays on: the root of xform<double, VCY_SQRT, RULES> with the seed taken from (float)x directly.  Kept elements get
+// the values they had, discarded ones added +-0: sums and results are the same bits (a NaN t is kept, as under `(|t| < 1e-16) ? 0 : ...`;
+// a NaN or inf in d[c] at a discarded gene no longer reaches sum A b as 0 * NaN, the result is NaN all the same through sum b).
+template <typename T, int TR, int RULES> struct ZeroMasked {
+    static constexpr bool value = std::is_same<T, double>::value && TR == VCY_SQRT && (RULES == VCY_RULES_PARTIAL || RULES == VCY_RULES_PARTIAL_ROOT2);
+};
+template <int RULES> __device__ __forceinline__ double xform_kept(double t, double psc)
+{
+    const double x = fabs(t) + psc;
+    const float xf = (float)x;
+    const float yf = __builtin_amdgcn_rsqf(xf);
+    const double s0 = (double)(xf * yf), h = (double)(0.5f * yf);
+    double d = fma(-s0, s0, x);
+    double s = fma(d, h, s0);
+    if (RULES == VCY_RULES_PARTIAL_ROOT2) {                      // the second Newton correction
+        d = fma(-s, s, x);
+        s = fma(d, h, s);
+    }
+    return copysign(s, t);
+}
 
 template <typename T, int TR, int RULES> __device__ __forceinline__ T xform_shift(T psc)
 {
@@ -619,12 +645,15 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
             while (mask) {
                 mask &= mask - 1;
                 const int mn = mask ? __builtin_ctz(mask) : m;
-                T sA, sAA, sAb, sAb2;                       // ONE partial sum per moment and lane: an element is 18 instructions, so the next add to an
-                                                            // accumulator is issued long after the last one landed; two interleaved partials cost three adds
-                                                            // per pair-chunk and six (f64: twelve) registers - f64 227.5 -> 226.2 ms, f64 dual 247.2 -> 236.5
-                                                            // (fewer spills), f32 70.8 -> 70.4
-                // (no zeroing: the first element of a pair initialises the sums; sum A^2 of the no-pseudocount rule is sum |t| - A^2 = |t|
+                T sA, sAA, sAb, sAb2;                       // ONE partial sum per moment and lane: an element is 15 (f64; f32: 8) or more instructions, so the
+                                                            // next add to an accumulator is issued long after the last one landed; two interleaved partials cost
+                                                            // three adds per pair-chunk and six (f64: twelve) registers - f64 227.5 -> 226.2 ms, f64 dual 247.2 ->
+                                                            // 236.5 (fewer spills), f32 70.8 -> 70.4
+                // (no zeroing: the first element of a pair initialises the sums - except under the zero mask, where that element's lane may be
+                //  off: those sums start at zero and every element updates them; sum A^2 of the no-pseudocount rule is sum |t| - A^2 = |t|
                 //  exactly for A = sign(t) sqrt|t|, one v_add with the |.| modifier that does not wait for the v_rsq_f32)
+                constexpr bool MASKED = ZeroMasked<T, TR, RULES>::value;
+                if constexpr (MASKED) { sA = sAA = sAb = T(0); if (DUAL) sAb2 = T(0); }
                 auto fold = [&](const V &xv, const V &ev, const V &bv, const V &b2v, bool first) {
                     const T *xp = reinterpret_cast<const T *>(&xv);
                     const T *ep = reinterpret_cast<const T *>(&ev);
@@ -634,6 +663,16 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
 #pragma unroll
                     for (int k = 0; k < N; ++k) {
                         const T tt = xp[k] - ep[k];
+                        if constexpr (MASKED) {
+                            if (!(fabs(tt) < 1e-16)) {                          // this form: a NaN t is a kept element
+                                const T a = xform_kept<RULES>(tt, psc);
+                                sA += a;
+                                sAA = fma(a, a, sAA);
+                                sAb = fma(a, bp[k], sAb);
+                                if (DUAL) sAb2 = fma(a, bp2[k], sAb2);
+                            }
+                            continue;
+                        }
                         const T a = xform_s<T, TR, RULES>(tt, psc, K);
                         if (first && k == 0) {
                             sA = a;
