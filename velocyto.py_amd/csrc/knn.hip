@@ -25,10 +25,14 @@
 // the threshold may hold more: that query alone recomputes its row and takes the radix-select path.
 // The exact distances are sums of ROUNDED squares in feature order (no fused multiply-add): two candidates whose
 // displacements are permutations / sign flips of each other then tie exactly, as they do in a plain C or numpy loop.
-// The fp32 pass only has to get the candidate SET right (margin of 8 near-ties); order and
-// returned distances are fp64, matching the reference's fp64 search up to exact ties (which
-// sklearn orders arbitrarily and this kernel orders by index; with include_self the query is an
-// ordinary candidate at distance 0).
+// The fp32 pass only has to get the candidate SET right: the exact re-rank takes the k best of a superset of the fp32
+// top-(k + 8).  Order and returned distances are fp64 (sums of rounded squares in feature order, sqrt correctly rounded),
+// ties by index where sklearn orders them arbitrarily; with include_self the query is an ordinary candidate at distance 0.
+// That equals the fp64 search of the reference on every query that is fp32-DECIDABLE: at most k + 8 candidates within the
+// fp32 error of the k-th distance - an error that follows the magnitude of the coordinates xt / qt hold, which is why the
+// callers hand over copies centred on the point set and scaled to [1, 2) (ops._knn_frame) and never the raw coordinates.
+// More than 8 fp32-indistinguishable candidates beyond rank k: a sorted, exact-distance list of candidates within the fp32
+// reach of the true one, not necessarily the true one.  The domain, the bound and the tests that hold it: DESIGN section 13.
 #include <math.h>
 #include "common.h"
 

@@ -903,6 +903,27 @@ def _knn_query_block(L, C: int, Q: int, k: int, query_block: int, budget: int = 
     return min(Q, max(query_block, (2 * budget // max(C, 1)) // 8 * 8))
 
 
+def _knn_f32_copy(dst: torch.Tensor, a64: torch.Tensor, frame) -> None:
+    """dst[:, :n] (feature-major f32) = (a64 - c) * scale for the frame (c, scale) of _knn_frame: rounded once in f64 (the scaling is
+    by a power of two) and once to f32."""
+    c, scale = frame
+    dst[:, :a64.shape[0]].copy_(((a64 - c) * scale).t())
+
+
+def _knn_frame(x64: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The frame (c, scale) of the f32 copies that the candidate pass of the search reads, (x - c) * scale: c the per-feature midpoint
+    of the point set, scale = 2^-e with e the exponent of the largest half-range (an exact scaling, into [-2, 2]).  The f32 pass
+    takes differences of coordinates, so its error follows the coordinates' magnitude: uncentred, a point set far from the origin
+    loses its neighbour structure to the rounding (at an offset of 2^20 the f32 coordinates are quantised to 0.125), and coordinates
+    beyond 2^64 or below 2^-75 square to inf or 0.  The exact f64 re-rank reads the untouched coordinates.  DESIGN section 13.
+    Everything stays on the device: no host synchronisation."""
+    mn, mx = torch.aminmax(x64, dim=0)
+    c = (mn + mx) * 0.5
+    m = ((mx - mn).amax() * 0.5).reshape(1)
+    field = (m.view(torch.int64) >> 52).clamp_(1, 2045)                  # biased exponent of m; zero / subnormal / non-finite clamped
+    return c, ((2046 - field) << 52).view(torch.float64)
+
+
 def knn_search(space, k: int, include_self: bool = False, q0: int = 0, Q: Optional[int] = None,
                query_block: int = 8192) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact Euclidean kNN of rows q0..q0+Q of `space` (C, P) among all C rows.
@@ -915,7 +936,7 @@ def knn_search(space, k: int, include_self: bool = False, q0: int = 0, Q: Option
         return _knn_search_segmented(x64, k, include_self, q0, Q, query_block)
     ldx = (C + 63) // 64 * 64
     xt = torch.zeros((P, ldx), dtype=torch.float32, device=dev)
-    xt[:, :C] = x64.t().float()
+    _knn_f32_copy(xt, x64, _knn_frame(x64))
     idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
     dist = torch.empty((Q, k), dtype=torch.float64, device=dev)
     L = _lib.lib()
@@ -1116,9 +1137,10 @@ def knn_query(points, queries, k: int, query_block: int = 8192) -> Tuple[torch.T
     assert q64.shape[1] == P and 0 < k <= C
     ldx, ldq = (C + 63) // 64 * 64, (Q + 63) // 64 * 64
     xt = torch.zeros((P, ldx), dtype=torch.float32, device=dev)
-    xt[:, :C] = x64.t().float()
+    frame = _knn_frame(x64)
+    _knn_f32_copy(xt, x64, frame)
     qt = torch.zeros((P, ldq), dtype=torch.float32, device=dev)
-    qt[:, :Q] = q64.t().float()
+    _knn_f32_copy(qt, q64, frame)                             # the queries in the frame of the POINT set
     idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
     dist = torch.empty((Q, k), dtype=torch.float64, device=dev)
     L = _lib.lib()
