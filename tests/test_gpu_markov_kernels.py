@@ -1,4 +1,4 @@
-"""Stage E/F and the Markov chain (csrc/misc.hip from k_corr_fixup down) against the long-double references of oracle.py, at the
+"""Stage E/F and the Markov chain (csrc/misc.hip from k_corr_fixup down, csrc/markov.hip) against the long-double references of oracle.py, at the
 ops wrapper or the C ABI, at the shapes where the kernels change path.  Every output is pre-filled with NaN or a sentinel.
 
 Tolerances - each is one of three things:

@@ -1371,7 +1371,7 @@ def test_f64_sqrt_element_accuracy_and_domain(ops, oracle):
 
 
 def test_f64_exp2_element_accuracy(ops):
-    """The fp64 Gauss-transform element of run_markov (csrc/misc.hip exp2_neg_tab: 2^(-d2) = 2^i T[j] 2^r from a 64-entry table and a
+    """The fp64 Gauss-transform element of run_markov (csrc/markov.hip exp2_neg_tab: 2^(-d2) = 2^i T[j] 2^r from a 64-entry table and a
     degree-5 polynomial, 11 f64 instructions where the degree-13 form took 17; exp2_neg_tab256 in the culled kernel) against numpy's exp2, element by element, through the real
     step kernels: one source cell at the origin with weight 1, targets at distance sqrt(d2) - y[j] = coef 2^(-d2_j) and nothing else.
     Within 1 ulp of exp2 plus the one rounding of the product with coef over [0, 1000]; beyond the clamp the value is below 1e-300
