@@ -71,7 +71,8 @@ const char *vcy_last_error(void);
  * vcy_knn_pool_csr requires >= 4 stored elements.  2 -> 3: vcy_clock_probe and vcy_coldeltacor_full_linear added.  3 -> 4: vcy_coldeltacor_full_linear_workspace_bytes takes C_out (repair flags); vcy_gemm_nt added.  A binder refuses a library whose version it was not built
  * against (velocyto_amd/_lib.py: EXPECTED_ABI).  (Round 7 added the enumerator VCY_RULES_PARTIAL_ROOT2: no argument list changed and every
  * value a version-4 caller passes is still accepted, so the version stays; such a caller's VCY_RULES_PARTIAL on VCY_SQRT / VCY_F64 now gets
- * the one-correction root described at vcy_rules.) */
+ * the one-correction root described at vcy_rules.)  (Gene selection from CSR layers added vcy_csr_gene_stats_block_cells,
+ * vcy_csr_gene_stats_workspace_bytes, vcy_csr_gene_stats, vcy_csr_select_count and vcy_csr_select_fill: additions only, the version stays.) */
 int vcy_abi_version(void);
 /* Number of CUs / LDS bytes per workgroup of the current device (host query). */
 int vcy_device_info(int *cu_count, int *lds_bytes_per_block, int64_t *hbm_bytes);
@@ -649,6 +650,32 @@ int vcy_csr_lognorm_spmm(const int64_t *indptr, const int32_t *indices, const vo
 int vcy_csr_lognorm_stats(const int64_t *indptr, const int32_t *indices, const void *data, const double *scale, double *stats,
                           void *workspace, int64_t R, int64_t N, int64_t nnz, int64_t max_row, double pcount, int scale_on,
                           int count_dtype, vcy_stream stream);
+
+/* ---------------------------------------------------------------- upstream caller: gene selection from CSR count layers
+ * score_detection_levels / score_cv_vs_mean / score_cluster_expression / filter_genes (analysis.py:214-345, 441-497; estimation.py:369-389)
+ * where the layers only exist as cells-major CSR counts (the atlas path): indptr int64 (C + 1), indices int32 gene numbers ascending
+ * inside a row, data counts as VCY_U8 or VCY_U16 bits, at least 4 stored elements allocated (as for vcy_knn_pool_csr).
+ * vcy_csr_gene_stats: stats (4, G) f64 = per gene [sum x, sum x^2, count(x > 0), max x] over the cells with cell_mask[c] != 0 (all cells
+ * when cell_mask is NULL) - the four rows of vcy_gene_stats, with no gene-major copy and no dense tile: a workgroup owns a tile of
+ * vcy_csr_gene_stats_block_cells() cells and one slab of vcy_csr_slab_genes() genes, found through slabptr (the table of
+ * vcy_csr_slab_ptr, (C, nslab + 1) int32), and accumulates in LDS with integer atomics; the tiles' partials (workspace:
+ * vcy_csr_gene_stats_workspace_bytes(C, G) bytes, 8-byte aligned) are added as integers.  Sums are unsigned 64-bit integers, the count
+ * and the maximum 32-bit, converted to f64 once: independent of order, hence bit-identical from run to run and for any split of the
+ * cells; sum x^2 <= 2^32 C is exact in f64 up to C = 2^21 cells of all-65535 counts and one correct rounding beyond.  An explicitly
+ * stored zero counts in nothing; genes with nothing stored give 0, 0, 0, 0 (so does every gene when no cell is selected, C == 0
+ * included - where vcy_gene_stats reports a maximum of -inf).  Masked-out rows are skipped whole.
+ * vcy_csr_select_count / vcy_csr_select_fill: the CSR of the genes g with remap[g] >= 0, renumbered remap[g] (remap: G int32, -1 = dropped;
+ * kept numbers distinct and below the new G - the caller's responsibility).  count writes row_len[r] = kept elements of row r; the
+ * caller forms indptr_out (C + 1; indptr_out[0] = 0, cumulative row_len) and allocates indptr_out[C] elements (both outputs non-NULL);
+ * fill writes them, the order of a row's elements preserved (ascending when remap is monotone).  One wave per row, rows are not cut. */
+int64_t vcy_csr_gene_stats_block_cells(void);
+size_t vcy_csr_gene_stats_workspace_bytes(int64_t C, int64_t G);
+int vcy_csr_gene_stats(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *slabptr, const uint8_t *cell_mask,
+                       double *stats, void *workspace, int64_t C, int64_t G, int count_dtype, vcy_stream stream);
+int vcy_csr_select_count(const int64_t *indptr, const int32_t *indices, const int32_t *remap, int64_t *row_len, int64_t C, int64_t G,
+                         vcy_stream stream);
+int vcy_csr_select_fill(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *remap, const int64_t *indptr_out,
+                        int32_t *indices_out, void *data_out, int64_t C, int64_t G, int count_dtype, vcy_stream stream);
 
 /* ---------------------------------------------------------------- host helper: neighbour sampling of estimate_transition_prob
  * analysis.py:1561-1564 draws, per cell, np.random.choice(n, size, replace=False, p=p) from numpy's legacy global RNG.  This is

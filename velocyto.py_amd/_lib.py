@@ -94,6 +94,11 @@ SIGNATURES = {
     "vcy_csr_spmm_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_csr_lognorm_spmm": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_dbl, c_int, c_int, c_vp]),
     "vcy_csr_lognorm_stats": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_dbl, c_int, c_int, c_vp]),
+    "vcy_csr_gene_stats_block_cells": (c_i64, []),
+    "vcy_csr_gene_stats_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vcy_csr_gene_stats": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
+    "vcy_csr_select_count": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "vcy_csr_select_fill": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
     "vcy_quantile_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_gene_quantiles": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_dbl), c_int, c_vp, c_vp, c_i64,
                                    c_i64, c_i64, c_int, c_vp]),

@@ -566,6 +566,114 @@ def synth_atlas(C: int, G: int, P: int, dev, density: float = 0.08, c0: int = 0,
     return cS, cU, cS.row_sums(), cU.row_sums(), pcs[c0:c1].contiguous(), emb[c0:c1].contiguous()
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# gene selection from the CSR count layers: velocyto's score_detection_levels / score_cv_vs_mean / score_cluster_expression /
+# filter_genes on the rank's shards (cells sharded as in AtlasPath).  The per-gene statistics are exact integers (vcy_csr_gene_stats),
+# so their all-reduce gives the one-rank bits whatever the sharding; the host arithmetic behind them is the facade's own
+# (preprocess.detection_mask, cv_vs_mean_from_stats, cluster_averages) and runs replicated on identical inputs: every function
+# returns numpy arrays that are the same on every rank.
+def total_cells(c: ops.CsrCounts) -> int:
+    """Cells of the whole dataset: the ranks' shard sizes added."""
+    n = torch.tensor([float(c.C)], dtype=torch.float64, device=c.indptr.device)
+    D.all_reduce_sum(n)
+    return int(round(float(n[0])))
+
+
+def gene_stats(c: ops.CsrCounts, cell_mask=None) -> np.ndarray:
+    """(4, G) float64 [sum, sum of squares, expressing cells, max] per gene over ALL ranks' cells (of the masked ones), on the host."""
+    st = ops.csr_gene_stats(c, cell_mask)
+    if D.active():
+        D.all_reduce_sum(st[:3])
+        D.all_reduce_max(st[3])
+    return st.cpu().numpy()
+
+
+def score_detection_levels(cS: ops.CsrCounts, cU: ops.CsrCounts, min_expr_counts: float = 50, min_cells_express: float = 20,
+                           min_expr_counts_U: float = 0, min_cells_express_U: float = 0) -> np.ndarray:
+    """analysis.py:456-475 on CSR layers: the facade's detection_level_selected."""
+    from .preprocess import detection_mask
+    return detection_mask(gene_stats(cS), gene_stats(cU), min_expr_counts, min_cells_express, min_expr_counts_U, min_cells_express_U)
+
+
+def score_cv_vs_mean(c: ops.CsrCounts, C_total: Optional[int] = None, N: int = 3000, min_expr_cells: int = 2, max_expr_avg: float = 20,
+                     min_expr_avg: float = 0, svr_gamma: Optional[float] = None, sort_inverse: bool = False,
+                     winsorize: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """analysis.py:201-345 on a CSR layer: (score, mask) = the facade's (cv_mean_score, cv_mean_selected); the SVR noise model
+    (preprocess.DeviceSVR) is fitted on every rank on the same points.  C_total: cells of the whole dataset (all-reduced when None)."""
+    if winsorize:
+        raise NotImplementedError("score_cv_vs_mean(winsorize=True) on CSR layers: the per-gene percentiles of a gene's stored counts over "
+                                  "the cells of a cells-major CSR are a separate piece of work (a streamed select over the layer); densify "
+                                  "and use VelocytoLoom.score_cv_vs_mean, or leave winsorize off")
+    from .preprocess import cv_vs_mean_from_stats
+    C_total = total_cells(c) if C_total is None else int(C_total)
+    return cv_vs_mean_from_stats(gene_stats(c), C_total, N=N, min_expr_cells=min_expr_cells, max_expr_avg=max_expr_avg,
+                                 min_expr_avg=min_expr_avg, svr_gamma=svr_gamma, sort_inverse=sort_inverse)
+
+
+def score_cluster_expression(cS: ops.CsrCounts, cU: ops.CsrCounts, cluster_ix, n_clusters: int, min_avg_U: float = 0.02,
+                             min_avg_S: float = 0.08, size_limit: int = 40) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """analysis.py:441-454 + estimation.py:369-389 on CSR layers: (U_avgs, S_avgs, mask), the averages (genes, clusters).  cluster_ix:
+    the cluster number (0..n_clusters-1) of each of the rank's own cells.  One masked pass per cluster of more than `size_limit`
+    cells - it reads that cluster's rows only - and the overall average for the others; cluster sizes are all-reduced."""
+    from .preprocess import cluster_averages, cluster_expression_mask
+    dev = cS.indptr.device
+    ix = torch.as_tensor(np.array(cluster_ix, dtype=np.int64), device=dev)
+    if ix.numel() != cS.C or cU.C != cS.C or cU.G != cS.G:
+        raise ValueError("score_cluster_expression: cS, cU and cluster_ix must describe the same cells and genes")
+    if ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= n_clusters):
+        raise ValueError(f"score_cluster_expression: cluster_ix outside 0..{n_clusters - 1}")
+    sizes = torch.bincount(ix, minlength=n_clusters).double()
+    D.all_reduce_sum(sizes)
+    sizes = [int(round(v)) for v in sizes.cpu().tolist()]
+    sums = lambda c, mask=None: gene_stats(c, mask)[0]
+    U_avgs, S_avgs = cluster_averages(sizes, total_cells(cS), cS.G, lambda i: (sums(cU, ix == i), sums(cS, ix == i)),
+                                      lambda: (sums(cU), sums(cS)), size_limit)
+    return U_avgs, S_avgs, cluster_expression_mask(U_avgs, S_avgs, min_avg_U, min_avg_S)
+
+
+def select_genes(keep, *layers: ops.CsrCounts) -> Tuple[ops.CsrCounts, ...]:
+    """filter_genes on CSR layers: every layer cut down to the genes `keep` (bool mask or ascending gene numbers)."""
+    return tuple(c.select_genes(keep) for c in layers)
+
+
+GENE_FILTER_THRESHOLDS = ("min_expr_counts", "min_cells_express", "N", "min_avg_U", "min_avg_S")
+
+
+def default_gene_thresholds(C_total: int, **given) -> Dict[str, float]:
+    """The thresholds of default_gene_filter: the cell-count heuristics of default_filter_and_norm (analysis.py:1909-1918;
+    PreprocessMixin._default_thresholds) unless passed."""
+    from .preprocess import PreprocessMixin
+    unknown = sorted(set(given) - set(GENE_FILTER_THRESHOLDS))
+    if unknown:
+        raise TypeError(f"default_gene_filter: unknown threshold(s) {unknown}; known: {list(GENE_FILTER_THRESHOLDS)}")
+    t = PreprocessMixin._default_thresholds(int(C_total))
+    return {**{k: t[k] for k in GENE_FILTER_THRESHOLDS}, **{k: v for k, v in given.items() if v is not None}}
+
+
+def default_gene_filter(cS: ops.CsrCounts, cU: ops.CsrCounts, cluster_ix=None, n_clusters: int = 0, **thresholds):
+    """The gene filters of default_filter_and_norm (analysis.py:1889-1940) on CSR layers, in its order: detection filter -> CV-vs-mean at
+    max_expr_avg = 40 -> detection filter on the unspliced layer with the halved thresholds, joined with the per-cluster expression
+    filter when clusters are given.  Returns (cS', cU', kept): the selected layers and the int64 gene numbers they hold, into the
+    layers as given (to subset the row attributes).  It stops before the normalisations: size_factors(cS'.row_sums(), ...) follows."""
+    C_total = total_cells(cS)
+    t = default_gene_thresholds(C_total, **thresholds)
+    kept = np.arange(cS.G, dtype=np.int64)
+
+    def cut(mask):
+        nonlocal cS, cU, kept
+        cS, cU = select_genes(mask, cS, cU)
+        kept = kept[mask]
+    cut(score_detection_levels(cS, cU, min_expr_counts=t["min_expr_counts"], min_cells_express=t["min_cells_express"]))
+    cut(score_cv_vs_mean(cS, C_total, N=t["N"], max_expr_avg=40)[1])
+    half = lambda x: int(x / 2) + 1
+    mask = score_detection_levels(cS, cU, min_expr_counts=0, min_cells_express=0, min_expr_counts_U=half(t["min_expr_counts"]),
+                                  min_cells_express_U=half(t["min_cells_express"]))
+    if cluster_ix is not None:
+        mask = mask & score_cluster_expression(cS, cU, cluster_ix, n_clusters, min_avg_U=t["min_avg_U"], min_avg_S=t["min_avg_S"])[2]
+    cut(mask)
+    return cS, cU, kept
+
+
 def size_factors(totS: torch.Tensor, totU: torch.Tensor, C: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """avg_size / cell_size of _normalize_S / _normalize_U (analysis.py:540-549, 570-579) with the mean over ALL cells."""
     sums = torch.stack([totS.sum(), totU.sum()])

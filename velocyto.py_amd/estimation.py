@@ -172,20 +172,12 @@ def clusters_stats(U, S, clusters_uid: np.ndarray, cluster_ix: np.ndarray, size_
     One masked streaming pass per cluster on the device (``vcy_gene_stats``).  U, S: (genes, cells) arrays or CellMatrix."""
     Ud, Sd = CellMatrix.from_genes_major(U, dtype), CellMatrix.from_genes_major(S, dtype)
     C, G = Sd.C, Sd.G
+    from .preprocess import cluster_averages                  # the arithmetic shared with the CSR route (atlas.score_cluster_expression)
     cluster_ix = np.asarray(cluster_ix)
-    U_avgs, S_avgs = np.zeros((G, len(clusters_uid))), np.zeros((G, len(clusters_uid)))
-    overall = None
-    for i, _ in enumerate(clusters_uid):
-        sel = cluster_ix == i
-        n = int(np.sum(sel))
-        if n > size_limit:
-            U_avgs[:, i] = ops.gene_stats(Ud, cell_mask=sel)[0].cpu().numpy() / n
-            S_avgs[:, i] = ops.gene_stats(Sd, cell_mask=sel)[0].cpu().numpy() / n
-        else:
-            if overall is None:
-                overall = (ops.gene_stats(Ud)[0].cpu().numpy() / C, ops.gene_stats(Sd)[0].cpu().numpy() / C)
-            U_avgs[:, i], S_avgs[:, i] = overall
-    return U_avgs, S_avgs
+    sels = [cluster_ix == i for i in range(len(clusters_uid))]
+    sums = lambda M, sel=None: ops.gene_stats(M, cell_mask=sel)[0].cpu().numpy()
+    return cluster_averages([int(np.sum(sel)) for sel in sels], C, G, lambda i: (sums(Ud, sels[i]), sums(Sd, sels[i])),
+                            lambda: (sums(Ud), sums(Sd)), size_limit)
 
 
 # --------------------------------------------------------------------------- one-gene forms (estimation.py:173-264)

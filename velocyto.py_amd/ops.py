@@ -351,6 +351,92 @@ class CsrCounts:
         ptr, idx, dat = transpose_csr(self.indptr, self.indices, self.data, self.G, block_nnz)
         return CsrCounts(ptr, idx, dat, self.C)
 
+    def select_genes(self, keep) -> "CsrCounts":
+        """The layer cut down to the genes `keep` - a bool mask of length G or an ascending list of gene numbers - as a new CsrCounts
+        with G = the number kept and the data dtype as it is (filter_genes, analysis.py:441-497, on the CSR: vcy_csr_select_count /
+        vcy_csr_select_fill; the only temporaries are G int32 + C int64).  max_row and slabptr are not inherited."""
+        return csr_select(self, *gene_remap(keep, self.G))
+
+
+def gene_remap(keep, G: int) -> Tuple[np.ndarray, int]:
+    """`keep` (bool mask of length G, or ascending gene numbers) -> (remap, G_new): remap[g] = the new number of gene g, or -1 (host)."""
+    k = np.asarray(keep)
+    if k.ndim != 1:
+        raise ValueError(f"keep must be one-dimensional, got shape {k.shape}")
+    if k.dtype == bool:
+        if k.size != G:
+            raise ValueError(f"a boolean keep needs one entry per gene: {k.size} given, G = {G}")
+        kept = np.flatnonzero(k)
+    elif np.issubdtype(k.dtype, np.integer) or k.size == 0:
+        kept = k.astype(np.int64)
+        if kept.size and (kept.min() < 0 or kept.max() >= G):
+            raise ValueError(f"keep holds gene numbers outside 0..{G - 1}")
+        if np.any(np.diff(kept) <= 0):
+            raise ValueError("an integer keep must be strictly ascending (a subset, not a permutation; no repeats)")
+    else:
+        raise ValueError(f"keep must be a bool mask or integer gene numbers, got dtype {k.dtype}")
+    remap = np.full(G, -1, dtype=np.int32)
+    remap[kept] = np.arange(kept.size, dtype=np.int32)
+    return remap, int(kept.size)
+
+
+def check_remap(remap, G: int, G_new: int) -> np.ndarray:
+    """What vcy_csr_select_* leave to the caller, checked on the host: G entries, every kept number below G_new and given once."""
+    r = np.ascontiguousarray(np.asarray(remap.cpu() if isinstance(remap, torch.Tensor) else remap), dtype=np.int32)
+    if r.ndim != 1 or r.size != G:
+        raise ValueError(f"remap needs one entry per gene: shape {r.shape}, G = {G}")
+    kept = r[r >= 0]
+    if kept.size and kept.max() >= G_new:
+        raise ValueError(f"remap holds new gene numbers >= the new G = {G_new}")
+    if np.unique(kept).size != kept.size:
+        raise ValueError("remap gives the same new gene number to more than one gene")
+    return r
+
+
+def csr_select(counts: CsrCounts, remap, G_new: int) -> CsrCounts:
+    """The CSR of the genes g with remap[g] >= 0, renumbered remap[g] (vcy_csr_select_count, torch's cumsum, vcy_csr_select_fill).  A
+    row's elements keep their order: a monotone remap (CsrCounts.select_genes) keeps the indices ascending."""
+    L = _lib.lib()
+    dev = counts.indptr.device
+    r = torch.from_numpy(check_remap(remap, counts.G, G_new)).to(dev)
+    C = counts.C
+    ptr = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+    if C and counts.G:
+        row_len = torch.empty(C, dtype=torch.int64, device=dev)
+        _lib.check(L.vcy_csr_select_count(counts.indptr.data_ptr(), counts._istore.data_ptr(), r.data_ptr(), row_len.data_ptr(), C, counts.G, _stream()),
+                   "csr_select_count")
+        torch.cumsum(row_len, 0, out=ptr[1:])
+        del row_len
+    total = int(ptr[-1])
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dat = torch.empty(total, dtype=counts.data.dtype, device=dev)
+    if total:
+        _lib.check(L.vcy_csr_select_fill(counts.indptr.data_ptr(), counts._istore.data_ptr(), counts._dstore.data_ptr(), r.data_ptr(), ptr.data_ptr(),
+                                         idx.data_ptr(), dat.data_ptr(), C, counts.G, counts.code, _stream()), "csr_select_fill")
+    return CsrCounts(ptr, idx, dat, G_new)
+
+
+def csr_gene_stats(counts: CsrCounts, cell_mask=None) -> torch.Tensor:
+    """(4, G) fp64 [sum, sum of squares, count(x > 0), max] per gene over the cells where cell_mask is true, straight from the cells-major
+    CSR layer (vcy_csr_gene_stats): the rows of gene_stats(counts.to_dense()), bit for bit, without the dense layer or the gene-major
+    copy.  Integer accumulation: independent of order and of how the cells are split.  Genes without a stored count give 0, 0, 0, 0."""
+    L = _lib.lib()
+    dev = counts.indptr.device
+    C, G = counts.C, counts.G
+    mask = None
+    if cell_mask is not None:
+        mask = torch.as_tensor(cell_mask, device=dev).to(torch.uint8).contiguous()
+        if mask.numel() != C:
+            raise ValueError(f"cell_mask needs one entry per cell: {mask.numel()} given, C = {C}")
+    out = torch.empty((4, G), dtype=torch.float64, device=dev)
+    if G == 0:
+        return out
+    n = int(L.vcy_csr_gene_stats_workspace_bytes(C, G))
+    ws = torch.empty(n // 8, dtype=torch.int64, device=dev) if n else None
+    _lib.check(L.vcy_csr_gene_stats(counts.indptr.data_ptr(), counts._istore.data_ptr(), counts._dstore.data_ptr(), counts.slabptr.data_ptr(),
+                                    _p(mask), out.data_ptr(), _p(ws), C, G, counts.code, _stream()), "csr_gene_stats")
+    return out
+
 
 def transpose_csr(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, G: int, block_nnz: int = 1 << 25):
     """(indptr, indices, data) of a (C, G) CSR with sorted rows -> the same of its (G, C) transpose, rows sorted.  Index plumbing

@@ -257,6 +257,72 @@ class DevicePCA:
         return (np.asarray(Xcg, dtype=np.float64) - self.mean_) @ self.components_.T
 
 
+# ---------------------------------------------------------------------- per-gene statistics -> gene masks
+# The host arithmetic of the gene scores, shared by the facade's methods below (statistics of the dense layers, vcy_gene_stats) and
+# the atlas route (statistics of the CSR layers, vcy_csr_gene_stats; atlas.score_*): both run the same float operations in the same
+# order, so equal statistics give equal masks and scores, bit for bit.  `st*`: (4, G) float64 [sum, sum of squares, count(x > 0), max].
+def detection_mask(sS: np.ndarray, sU: np.ndarray, min_expr_counts: float = 50, min_cells_express: float = 20, min_expr_counts_U: float = 0,
+                   min_cells_express_U: float = 0) -> np.ndarray:
+    """analysis.py:456-475: genes with enough molecules and enough expressing cells in both layers."""
+    return ((sS[0] >= min_expr_counts) & (sS[2] >= min_cells_express) &
+            (sU[0] >= min_expr_counts_U) & (sU[2] >= min_cells_express_U))
+
+
+def cv_vs_mean_from_stats(st: np.ndarray, C: int, N: int = 3000, min_expr_cells: int = 2, max_expr_avg: float = 20, min_expr_avg: float = 0,
+                          svr_gamma: float = None, sort_inverse: bool = False, moments: np.ndarray = None) -> Tuple[np.ndarray, np.ndarray]:
+    """analysis.py:253-345 from the per-gene statistics over C cells: (score, selected) - the CV-vs-mean score of every gene (the
+    undetected ones just under the smallest) and the mask of the N + 1 genes most above the SVR noise model (DeviceSVR).  `moments`:
+    the statistics the mean and the variance are taken from when they are not `st` (the winsorised values)."""
+    mean_all = st[0] / C
+    detected_bool = (st[2] > min_expr_cells) & (mean_all < max_expr_avg) & (mean_all > min_expr_avg)
+    if moments is not None:
+        st = moments
+    mu = (st[0] / C)[detected_bool]
+    var = (st[1][detected_bool] - C * mu * mu) / (C - 1)
+    sigma = np.sqrt(np.maximum(var, 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cv = sigma / mu
+        log_m, log_cv = np.log2(mu), np.log2(cv)
+    if svr_gamma is None:
+        svr_gamma = 150. / len(mu)
+        logging.debug(f"svr_gamma set to {svr_gamma}")
+    clf = DeviceSVR(gamma=svr_gamma)
+    clf.fit(log_m[:, None], log_cv)
+    score = log_cv - clf.predict(log_m[:, None])
+    if sort_inverse:
+        score = -score
+    nth_score = np.sort(score)[::-1][N]
+    full = np.zeros(detected_bool.shape)
+    full[~detected_bool] = np.min(score) - 1e-16
+    full[detected_bool] = score
+    return full, full >= nth_score
+
+
+def cluster_averages(sizes, n_cells: int, n_genes: int, cluster_sums, overall_sums, size_limit: int = 40) -> Tuple[np.ndarray, np.ndarray]:
+    """estimation.py:369-389: (U_avgs, S_avgs), each (genes, clusters) - the per-gene average over the cells of every cluster of more than
+    `size_limit` cells, the overall average for the others.  sizes[i]: cells of cluster i; cluster_sums(i) -> the per-gene sums (U, S)
+    over the cells of cluster i; overall_sums() -> the same over all n_cells cells (asked for at most once, when first needed)."""
+    U_avgs, S_avgs = np.zeros((n_genes, len(sizes))), np.zeros((n_genes, len(sizes)))
+    overall = None
+    for i, n in enumerate(sizes):
+        n = int(n)
+        if n > size_limit:
+            sU, sS = cluster_sums(i)
+            U_avgs[:, i] = sU / n
+            S_avgs[:, i] = sS / n
+        else:
+            if overall is None:
+                sU, sS = overall_sums()
+                overall = (sU / n_cells, sS / n_cells)
+            U_avgs[:, i], S_avgs[:, i] = overall
+    return U_avgs, S_avgs
+
+
+def cluster_expression_mask(U_avgs: np.ndarray, S_avgs: np.ndarray, min_avg_U: float = 0.02, min_avg_S: float = 0.08) -> np.ndarray:
+    """analysis.py:441-454: genes whose largest cluster average passes both thresholds."""
+    return (U_avgs.max(1) > min_avg_U) & (S_avgs.max(1) > min_avg_S)
+
+
 class PreprocessMixin:
     """Methods of VelocytoLoom upstream of knn_imputation (mixed into analysis.VelocytoLoom)."""
 
@@ -381,8 +447,7 @@ class PreprocessMixin:
         """analysis.py:456-475: detection_level_selected from per-gene totals and numbers of expressing cells."""
         sS = ops.gene_stats(self._layer_for_stats("S")).cpu().numpy()
         sU = ops.gene_stats(self._layer_for_stats("U")).cpu().numpy()
-        self.detection_level_selected = ((sS[0] >= min_expr_counts) & (sS[2] >= min_cells_express) &
-                                         (sU[0] >= min_expr_counts_U) & (sU[2] >= min_cells_express_U))
+        self.detection_level_selected = detection_mask(sS, sU, min_expr_counts, min_cells_express, min_expr_counts_U, min_cells_express_U)
 
     def score_cv_vs_mean(self, N: int = 3000, min_expr_cells: int = 2, max_expr_avg: float = 20, min_expr_avg: int = 0, svr_gamma: float = None,
                          winsorize: bool = False, winsor_perc: Tuple[float, float] = (1, 99.5), sort_inverse: bool = False, which: str = "S",
@@ -398,40 +463,23 @@ class PreprocessMixin:
                 min_expr_cells = int(np.ceil((100 - winsor_perc[1]) * G * 0.01)) + 2          # sic: genes, as the reference (:248)
                 logging.debug(f"min_expr_cells is too low for winsorization with upper_perc ={winsor_perc[1]}, upgrading to min_expr_cells ={min_expr_cells}")
         st = ops.gene_stats(M).cpu().numpy()
-        mean_all = st[0] / C
-        detected_bool = (st[2] > min_expr_cells) & (mean_all < max_expr_avg) & (mean_all > min_expr_avg)
+        moments = None
         if winsorize:
             q = ops.gene_quantiles(self.dev(name), list(winsor_perc))
-            st = ops.gene_stats(M, lo=q[0], hi=q[1]).cpu().numpy()
-        mu = (st[0] / C)[detected_bool]
-        var = (st[1][detected_bool] - C * mu * mu) / (C - 1)
-        sigma = np.sqrt(np.maximum(var, 0.0))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            cv = sigma / mu
-            log_m, log_cv = np.log2(mu), np.log2(cv)
-        if svr_gamma is None:
-            svr_gamma = 150. / len(mu)
-            logging.debug(f"svr_gamma set to {svr_gamma}")
-        clf = DeviceSVR(gamma=svr_gamma)
-        clf.fit(log_m[:, None], log_cv)
-        score = log_cv - clf.predict(log_m[:, None])
-        if sort_inverse:
-            score = -score
-        nth_score = np.sort(score)[::-1][N]
-        full = np.zeros(detected_bool.shape)
-        full[~detected_bool] = np.min(score) - 1e-16
-        full[detected_bool] = score
+            moments = ops.gene_stats(M, lo=q[0], hi=q[1]).cpu().numpy()
+        full, selected = cv_vs_mean_from_stats(st, C, N=N, min_expr_cells=min_expr_cells, max_expr_avg=max_expr_avg, min_expr_avg=min_expr_avg,
+                                               svr_gamma=svr_gamma, sort_inverse=sort_inverse, moments=moments)
         if which == "S":
-            self.cv_mean_score, self.cv_mean_selected = full, full >= nth_score
+            self.cv_mean_score, self.cv_mean_selected = full, selected
         else:
-            self.Ucv_mean_score, self.Ucv_mean_selected = full, full >= nth_score
+            self.Ucv_mean_score, self.Ucv_mean_selected = full, selected
 
     def score_cluster_expression(self, min_avg_U: float = 0.02, min_avg_S: float = 0.08) -> None:
         """analysis.py:441-454 + estimation.clusters_stats (estimation.py:369-389): per-cluster gene averages (clusters of
         at most 40 cells report the overall average), masked streaming passes on the device."""
         from .estimation import clusters_stats
         self.U_avgs, self.S_avgs = clusters_stats(self.dev("U"), self.dev("S"), self.cluster_uid, self.cluster_ix, size_limit=40)
-        self.clu_avg_selected = (self.U_avgs.max(1) > min_avg_U) & (self.S_avgs.max(1) > min_avg_S)
+        self.clu_avg_selected = cluster_expression_mask(self.U_avgs, self.S_avgs, min_avg_U, min_avg_S)
 
     def robust_size_factor(self, pc: float = 0.1, which: str = "both") -> None:
         """analysis.py:347-439: per-cell median over the selected genes of 2**(log2(x + pc) - gene mean of log2), mean 1."""
