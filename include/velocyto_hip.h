@@ -222,8 +222,12 @@ int vcy_knn_pool_counts(const void *countsS, const void *countsU, const double *
  * C x (ceil(G / vcy_csr_slab_genes()) + 1) int32 = offsets inside each row of the first non-zero of every gene slab.
  * `indices` and `data` must hold at least 4 elements (the kernel reads quads of consecutive non-zeros with 16-byte loads,
  * pulled back to end inside the arrays): a layer with fewer than 4 non-zeros is padded by the caller; elements at or past
- * indptr[C] belong to no row and never enter a result.  */
+ * indptr[C] belong to no row and never enter a result.
+ * vcy_knn_pool_csr_splits(C_out, G): the number of waves the launcher spreads a cell's ceil(G / vcy_csr_slab_genes()) slabs
+ * over - ceil(20480 / C_out), at most one per slab, no empty range; a wave walks ceil(slabs / splits) consecutive slabs (the
+ * last range may be shorter).  0 for C_out <= 0 or G <= 0.  A query: results do not depend on it.  */
 int64_t vcy_csr_slab_genes(void);
+int vcy_knn_pool_csr_splits(int64_t C_out, int64_t G);
 int vcy_csr_slab_ptr(const int64_t *indptr, const int32_t *indices, int32_t *slabptr, int64_t C, int64_t G, vcy_stream stream);
 int vcy_knn_pool_csr(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *slabptr, const double *scale,
                      void *out, const int64_t *g_indptr, const int32_t *g_indices, const void *w, const int32_t *order, int64_t C,

@@ -1095,6 +1095,74 @@ def gauss_step_emulated(x, tot, kw, colptr, rowidx, scsc, es, sigma_W, dtype, ga
     return g if gauss_only else _csc_half(v, colptr, rowidx, scsc, np.float64) + g
 
 
+# --------------------------------------------------------------------------- long-double reference of stage A (kNN pooling)
+def pool_reference(indptr, indices, w, data, scale=None, maximum=False, cell0=0):
+    """Stage A in long double on the inputs as the device holds them: out[r, :] = sum_p (w[p] scale[j_p]) data[j_p, :] over the
+    entries p of graph row r (neighbors.py:416-423 applied to S_sz = scale * S, analysis.py:546-549, 1011-1016).  data: (C, G)
+    CELLS-major, floats already rounded to the working type or integer counts; w already rounded to the working type; scale: (C)
+    f64 or None (ones); the graph rows name rows of data, repeats allowed, an empty row pools to 0.  maximum: np.maximum with the
+    output cell's own scaled row (analysis.py:1017-1019), row cell0 + r of data (cell0: an int, or the own row of every output row).
+    Returns (out, A) with A[r, g] = sum_p |w[p] scale[j_p] data[j_p, g]|, what the rounding error of any summation order scales
+    with, and with `maximum` also own[r, g] = |scale[own] data[own, g]|."""
+    indptr, indices = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    X = np.asarray(data).astype(_LD)
+    s = np.ones(X.shape[0], dtype=_LD) if scale is None else np.asarray(scale, dtype=np.float64).astype(_LD)
+    wl = np.asarray(w).astype(_LD)
+    R = indptr.size - 1
+    out, A = np.zeros((R, X.shape[1]), dtype=_LD), np.zeros((R, X.shape[1]), dtype=_LD)
+    for r in range(R):
+        j = indices[indptr[r]:indptr[r + 1]]
+        if j.size:
+            t = (wl[indptr[r]:indptr[r + 1]] * s[j])[:, None] * X[j]
+            out[r], A[r] = t.sum(0), np.abs(t).sum(0)
+    if not maximum:
+        return out, A
+    me = (cell0 + np.arange(R)) if np.ndim(cell0) == 0 else np.asarray(cell0, dtype=np.int64)
+    own = s[me][:, None] * X[me]
+    return np.maximum(out, own), A, np.abs(own)
+
+
+def pool_bound(A, n_terms, dtype, counts, own=None):
+    """The derived bound on |device - pool_reference| per output element; nothing in it is measured.  The device adds a row's n terms
+    in graph order with one fma each, acc = fma(ws, x, acc): the recursive-sum bound gamma_n A <= (n + 2) u A (n^2 u << 1).  Pooling
+    from counts rounds twice more per term, (T)scale[j] and w * (T)scale: (n + 4) u A.  With `own` (maximum) the result is
+    max(sum, own term); max is 1-Lipschitz in each argument and the own term fl((T)scale * x) carries two roundings, so the bound
+    is max(that, 2 u own).  u = 2^-24 (float32) or 2^-53 (float64); n_terms: entries per graph row, shape (R,).  Where A == 0 (and
+    own == 0) the bound is 0: the output must be exactly 0."""
+    u = {"float32": 2.0 ** -24, "float64": 2.0 ** -53}[np.dtype(dtype).name]
+    n = np.asarray(n_terms, dtype=np.float64)[:, None]
+    b = ((n + (4.0 if counts else 2.0)) * u * np.asarray(A, dtype=_LD)).astype(np.float64)
+    return b if own is None else np.maximum(b, 2.0 * u * np.asarray(own, dtype=np.float64))
+
+
+def pool_emulated(indptr, indices, w, data, scale, dtype, maximum=False, cell0=0):
+    """The device's chain in numpy arithmetic of `dtype`, without an fma: graph order, ws = w * (T)scale[j] where there is a scale,
+    then per term one rounded product and one rounded add in float64, and in float32 product and sum formed in f64 and rounded to
+    f32 once per step (the f64 product of two f32 numbers is exact: this is the fma but for a double rounding).  Only a measuring
+    stick: it shows that a plain implementation meets pool_bound (with n doubled for the unfused f64 form)."""
+    dt = np.dtype(dtype).type
+    indptr, indices = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    X = np.asarray(data).astype(dt)
+    wt = np.asarray(w).astype(dt)
+    st = None if scale is None else np.asarray(scale, dtype=np.float64).astype(dt)
+    R = indptr.size - 1
+    out = np.zeros((R, X.shape[1]), dtype=dt)
+    for r in range(R):
+        acc = np.zeros(X.shape[1], dtype=dt)
+        for p in range(indptr[r], indptr[r + 1]):
+            j = indices[p]
+            ws = wt[p] if st is None else dt(wt[p] * st[j])
+            if dt is np.float32:
+                acc = (acc.astype(np.float64) + np.float64(ws) * X[j].astype(np.float64)).astype(np.float32)
+            else:
+                acc = acc + ws * X[j]
+        out[r] = acc
+    if maximum:
+        me = (cell0 + np.arange(R)) if np.ndim(cell0) == 0 else np.asarray(cell0, dtype=np.int64)
+        out = np.maximum(out, X[me] if st is None else st[me][:, None] * X[me])
+    return out
+
+
 # --------------------------------------------------------------------------- "next" rows (SURVEY.md section 8f)
 def knn_query(points, queries, k) -> Tuple[np.ndarray, np.ndarray]:
     """NearestNeighbors(...).fit(points).kneighbors(queries): exact fp64 brute force, nearest first, ties by index."""

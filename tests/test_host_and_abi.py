@@ -30,6 +30,24 @@ def test_header_symbols_exported(lib):
     # and the maintainer's guide names every one of them (which reference call it replaces, or what a binder needs it for)
     guide = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert not [n for n in sorted(declared) if n not in guide]
+    assert "vcy_knn_pool_csr_splits" in declared
+
+
+def test_knn_pool_csr_splits(lib):
+    """The launcher's own rule, read back (host code, no GPU): ceil(20480 / C_out) waves per cell, at most one per slab of
+    vcy_csr_slab_genes() genes, no empty range."""
+    L = lib.lib()
+    slab = int(L.vcy_csr_slab_genes())
+    assert slab == 2048
+    for C_out, G, want in ((1, 1, 1), (1, 4097, 3), (10240, 4097, 2), (10241, 4097, 2), (20480, 4097, 1), (20481, 4097, 1),
+                           (6827, 4097, 3), (6826, 4097, 3), (300, 2048, 1), (300, 2049, 2), (5000, 30000, 5), (4096, 30000, 5),
+                           (1000, 30000, 15), (200000, 30000, 1), (0, 10, 0), (10, 0, 0), (-1, 10, 0)):
+        assert L.vcy_knn_pool_csr_splits(C_out, G) == want, (C_out, G)
+    for C_out in (1, 7, 1500, 3000, 5000, 9000, 20479):                   # every range holds a slab, the ranges cover all of them
+        for G in (1, 2048, 2049, 30000, 65536):
+            nslab, ns = (G + slab - 1) // slab, L.vcy_knn_pool_csr_splits(C_out, G)
+            sper = (nslab + ns - 1) // ns
+            assert 1 <= ns <= min(nslab, (20480 + C_out - 1) // C_out) and (ns - 1) * sper < nslab <= ns * sper
 
 
 def test_no_cpu_fallback_in_product():

@@ -123,6 +123,33 @@ def test_pool_args(ops, as_tensor):
         with pytest.raises(ValueError, match="neighbour index out of range"):
             ops._pool_args(cpu, torch.float32, n_rows, C_out, conv(indptr), conv(ixb), (conv(w),), None, True)
         assert ops._pool_args(cpu, torch.float32, n_rows, C_out, conv(indptr), conv(ixb), (conv(w),), None, False)[1].tolist() == ixb.tolist()
+    # indptr: starts at 0, never decreases, ends at len(indices) - a row outside that reads (and, in the CSR kernel, writes) out of bounds
+    for bad in ([1, 2, 2, 5], [0, 3, 2, 5], [0, 2, 2, 4], [0, 2, 2, 6], [0, 6, 6, 5]):
+        with pytest.raises(ValueError, match="indptr must start at 0"):
+            ops._pool_args(cpu, torch.float32, n_rows, C_out, conv(np.array(bad, dtype=np.int64)), conv(indices), (conv(w),), None, True)
+        assert ops._pool_args(cpu, torch.float32, n_rows, C_out, conv(np.array(bad, dtype=np.int64)), conv(indices), (conv(w),), None, False)[0].tolist() == bad
+    # order: a permutation of range(C_out) - a repeated cell leaves another unwritten, a cell out of range is written out of bounds
+    for bad in ([0, 1, 1], [0, 1, 3], [-1, 0, 1], [2, 2, 2]):
+        ob = torch.tensor(bad, dtype=torch.int64)
+        with pytest.raises(ValueError, match="order must be a permutation"):
+            ops._pool_args(cpu, torch.float32, n_rows, C_out, conv(indptr), conv(indices), (conv(w),), ob, True)
+        assert ops._pool_args(cpu, torch.float32, n_rows, C_out, conv(indptr), conv(indices), (conv(w),), ob, False)[3].tolist() == bad
+    assert ops._pool_args(cpu, torch.float32, n_rows, C_out, conv(indptr), conv(indices), (conv(w),), np.array([1, 2, 0]), True)[3].tolist() == [1, 2, 0]
+    empty = ops._pool_args(cpu, torch.float32, n_rows, 2, conv(np.zeros(3, dtype=np.int64)), conv(indices[:0]), (conv(w[:0]),), None, True)
+    assert empty[0].tolist() == [0, 0, 0] and empty[1].numel() == 0
+
+
+def test_check_pool_out(ops):
+    """ops._check_pool_out, what knn_pool / knn_pool2 / knn_pool_counts ask of an `out=` buffer BEFORE they launch: rows for every
+    output cell, the gene count and dtype of the result and - for the kernels that take one leading dimension for input and
+    output - that leading dimension.  (A stand-in with the four attributes: CellMatrix itself only holds device tensors.)"""
+    from types import SimpleNamespace as NS
+    ok = NS(C=5, G=70, dtype=torch.float32, ld=128)
+    ops._check_pool_out(ok, 5, 70, torch.float32, 128)
+    ops._check_pool_out(ok, 3, 70, torch.float32)                       # more rows than C_out are fine, ld unconstrained
+    for args in ((6, 70, torch.float32, 128), (5, 71, torch.float32, 128), (5, 70, torch.float64, 128), (5, 70, torch.float32, 64)):
+        with pytest.raises(AssertionError, match="out= buffer"):
+            ops._check_pool_out(ok, *args)
 
 
 def test_scale_vec(ops):

@@ -50,6 +50,7 @@ SIGNATURES = {
     "vcy_knn_pool_counts": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
                                     c_int, c_i64, c_int, c_int, c_vp]),
     "vcy_csr_slab_genes": (c_i64, []),
+    "vcy_knn_pool_csr_splits": (c_int, [c_i64, c_i64]),
     "vcy_csr_slab_ptr": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "vcy_knn_pool_csr": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
                                  c_int, c_int, c_int, c_vp]),

@@ -211,6 +211,19 @@ extern "C" int vcy_csr_slab_ptr(const int64_t *indptr, const int32_t *indices, i
     return VCY_OK;
 }
 
+// a wave walks a contiguous range of slabs of its cell; few output cells (halo rows, small blocks) split the slabs over
+// more waves so that the launch still fills the 256 CUs x 20 resident waves
+extern "C" int vcy_knn_pool_csr_splits(int64_t C_out, int64_t G)
+{
+    if (C_out <= 0 || G <= 0) return 0;
+    const int64_t nslab = (G + CSR_SLAB - 1) / CSR_SLAB;
+    int64_t nsplit = (4 * 5120 + C_out - 1) / C_out;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > nslab) nsplit = nslab;
+    const int64_t sper = (nslab + nsplit - 1) / nsplit;
+    return (int)((nslab + sper - 1) / sper);                // no empty ranges
+}
+
 extern "C" int vcy_knn_pool_csr(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *slabptr, const double *scale,
                                 void *out, const int64_t *g_indptr, const int32_t *g_indices, const void *w, const int32_t *order, int64_t C,
                                 int64_t G, int64_t ld_out, int64_t cell0, int64_t C_out, int maximum, int count_dtype, int dtype, vcy_stream stream)
@@ -221,12 +234,7 @@ extern "C" int vcy_knn_pool_csr(const int64_t *indptr, const int32_t *indices, c
     VCY_REQUIRE(dtype == VCY_F32 || dtype == VCY_F64, "knn_pool_csr: bad dtype");
     VCY_REQUIRE(ld_out % 16 == 0 && ((uintptr_t)out % 16) == 0, "knn_pool_csr: output rows must be 16-byte aligned with ld_out % 16 == 0");
     const int64_t nslab = (G + CSR_SLAB - 1) / CSR_SLAB;
-    // a wave walks a contiguous range of slabs of its cell; few output cells (halo rows, small blocks) split the slabs over
-    // more waves so that the launch still fills the 256 CUs x 20 resident waves
-    int64_t nsplit = (4 * 5120 + C_out - 1) / C_out;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > nslab) nsplit = nslab;
-    nsplit = (nslab + ((nslab + nsplit - 1) / nsplit) - 1) / ((nslab + nsplit - 1) / nsplit);      // no empty ranges
+    const int64_t nsplit = vcy_knn_pool_csr_splits(C_out, G);
     const int64_t nquads = (C_out + CSR_WAVES - 1) / CSR_WAVES, blocks = nsplit * ((nquads + 7) / 8 * 8);
     VCY_REQUIRE(blocks < (1LL << 31), "knn_pool_csr: grid too large");
     hipStream_t st = as_stream(stream);

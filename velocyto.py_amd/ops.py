@@ -642,17 +642,23 @@ def _as_i32(ixs, dev) -> torch.Tensor:
 
 def _pool_args(dev, dt, n_rows: int, C_out: int, indptr, indices, weights: Sequence, order, validate: bool):
     """The graph arguments of the pooling entry points (numpy arrays or tensors) as contiguous tensors on `dev`: (indptr int64,
-    indices int32, the weight vectors in `dt`, order int32 or None).  `validate` range-checks the indices against the `n_rows` rows
-    of the pooled matrix (a device->host sync)."""
+    indices int32, the weight vectors in `dt`, order int32 or None).  `validate` (device->host syncs) checks what the kernels take on
+    trust: every index names one of the `n_rows` rows of the pooled matrix, indptr starts at 0, never decreases and ends at
+    len(indices), and `order` is a permutation of range(C_out) - anything else reads or writes out of bounds.  ValueError, before any launch."""
     ip = (indptr if isinstance(indptr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(indptr).astype(np.int64))).to(device=dev, dtype=torch.int64).contiguous()
     ix = _as_i32(indices, dev)
     ws = tuple((w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w))).to(device=dev, dtype=dt).contiguous() for w in weights)
     assert ip.numel() == C_out + 1 and all(w.numel() == ix.numel() for w in ws)
     if validate and ix.numel() and (int(ix.min()) < 0 or int(ix.max()) >= n_rows):
         raise ValueError("neighbour index out of range")
+    if validate and (int(ip[0]) != 0 or int(ip[-1]) != ix.numel() or bool((ip[1:] < ip[:-1]).any())):
+        raise ValueError("indptr must start at 0, never decrease and end at len(indices)")
     if order is not None:
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
+        order = (order if isinstance(order, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(order))).to(device=dev)
         assert order.numel() == C_out
+        if validate and not torch.equal(torch.sort(order.reshape(-1).to(torch.int64)).values, torch.arange(C_out, device=dev)):
+            raise ValueError("order must be a permutation of range(C_out)")
+        order = order.to(torch.int32).contiguous()
     return ip, ix, ws, order
 
 
@@ -909,6 +915,21 @@ def canonical_graph_rows(indices: torch.Tensor, weights: torch.Tensor) -> Tuple[
     return srt.contiguous(), weights.gather(1, perm).contiguous()
 
 
+def _check_pool_out(out: "CellMatrix", C_out: int, G: int, dt: torch.dtype, ld: Optional[int] = None) -> None:
+    """A caller's `out=` buffer of a pooling entry point: rows for every output cell, the pooled matrix's gene count and dtype and,
+    where the launch takes ONE leading dimension for input and output (the float kernels; the two outputs of the count kernel), that
+    leading dimension - any other buffer would be written out of bounds."""
+    assert out.C >= C_out and out.G == G and out.dtype == dt, "out= buffer: fewer rows than C_out, another gene count or another dtype"
+    assert ld is None or out.ld == ld, "out= buffer: another leading dimension than the launch uses"
+
+
+def _pool_out_like(data: "CellMatrix", C_out: int) -> "CellMatrix":
+    """The output of a float pooling launch: C_out rows with the INPUT's leading dimension (the launch takes one for both), padding zeroed."""
+    t = torch.empty((C_out, data.ld), dtype=data.dtype, device=data.t.device)
+    t[:, data.G:].zero_()
+    return CellMatrix(t, data.G)
+
+
 def knn_pool(data: CellMatrix, indptr, indices, weights, maximum: bool = False, cell0: int = 0,
              C_out: Optional[int] = None, slab_genes: int = 0, out: Optional[CellMatrix] = None,
              validate: bool = True, order: Optional[torch.Tensor] = None) -> CellMatrix:
@@ -916,8 +937,8 @@ def knn_pool(data: CellMatrix, indptr, indices, weights, maximum: bool = False, 
     dev = data.t.device
     C_out = data.C - cell0 if C_out is None else C_out
     ip, ix, (w,), order = _pool_args(dev, data.dtype, data.C, C_out, indptr, indices, (weights,), order, validate)
-    if out is None:
-        out = CellMatrix.empty(C_out, data.G, data.dtype)
+    out = _pool_out_like(data, C_out) if out is None else out
+    _check_pool_out(out, C_out, data.G, data.dtype, data.ld)
     _lib.check(_lib.lib().vcy_knn_pool(data.t.data_ptr(), out.t.data_ptr(), ip.data_ptr(), ix.data_ptr(), w.data_ptr(), _p(order), data.C,
                                        data.G, data.ld, cell0, C_out, int(maximum), int(slab_genes), data.code, _stream()), "knn_pool")
     return out
@@ -930,7 +951,7 @@ def knn_pool_w2(data: CellMatrix, indptr, indices, weights, weights2, cell0: int
     dev = data.t.device
     C_out = data.C - cell0 if C_out is None else C_out
     ip, ix, (w, w2), order = _pool_args(dev, data.dtype, data.C, C_out, indptr, indices, (weights, weights2), order, validate)
-    out, out2 = CellMatrix.empty(C_out, data.G, data.dtype), CellMatrix.empty(C_out, data.G, data.dtype)
+    out, out2 = _pool_out_like(data, C_out), _pool_out_like(data, C_out)
     _lib.check(_lib.lib().vcy_knn_pool_w2(data.t.data_ptr(), out.t.data_ptr(), out2.t.data_ptr(), ip.data_ptr(), ix.data_ptr(), w.data_ptr(),
                                           w2.data_ptr(), _p(order), data.C, data.G, data.ld, cell0, C_out, int(slab_genes), data.code, _stream()),
                "knn_pool_w2")
@@ -945,8 +966,10 @@ def knn_pool2(data: CellMatrix, data2: CellMatrix, indptr, indices, weights, max
     assert data.t.shape == data2.t.shape and data.dtype == data2.dtype and data.G == data2.G
     C_out = data.C - cell0 if C_out is None else C_out
     ip, ix, (w,), order = _pool_args(dev, data.dtype, data.C, C_out, indptr, indices, (weights,), order, validate)
-    out = CellMatrix.empty(C_out, data.G, data.dtype) if out is None else out
-    out2 = CellMatrix.empty(C_out, data.G, data.dtype) if out2 is None else out2
+    out = _pool_out_like(data, C_out) if out is None else out
+    out2 = _pool_out_like(data, C_out) if out2 is None else out2
+    _check_pool_out(out, C_out, data.G, data.dtype, data.ld)
+    _check_pool_out(out2, C_out, data.G, data.dtype, data.ld)
     _lib.check(_lib.lib().vcy_knn_pool2(data.t.data_ptr(), out.t.data_ptr(), data2.t.data_ptr(), out2.t.data_ptr(), ip.data_ptr(), ix.data_ptr(),
                                         w.data_ptr(), _p(order), data.C, data.G, data.ld, cell0, C_out, int(maximum), int(slab_genes), data.code,
                                         _stream()), "knn_pool2")
@@ -974,6 +997,8 @@ def knn_pool_counts(cS: CountMatrix, cU: Optional[CountMatrix], scaleS, scaleU, 
     out = CellMatrix.empty(C_out, cS.G, dt) if out is None else out
     if cU is not None:
         out2 = CellMatrix.empty(C_out, cS.G, dt) if out2 is None else out2
+        _check_pool_out(out2, C_out, cS.G, dt, out.ld)             # (the launch takes one ld_out for both outputs)
+    _check_pool_out(out, C_out, cS.G, dt)
     _lib.check(_lib.lib().vcy_knn_pool_counts(cS.t.data_ptr(), None if cU is None else cU.t.data_ptr(), sS.data_ptr(), _p(sU), out.t.data_ptr(),
                                               None if cU is None else out2.t.data_ptr(), ip.data_ptr(), ix.data_ptr(), w.data_ptr(), _p(order),
                                               cS.C, cS.G, cS.ld, out.ld, cell0, C_out, int(maximum), int(slab_genes), cS.code, out.code, _stream()),
