@@ -274,6 +274,32 @@ int vcy_balance_knn_host(const int64_t *dsi_host, const double *dist_host, const
 int vcy_balance_knn_host32(const int32_t *dsi_host, const int64_t *lsi_host, const int64_t *groups_host, int64_t n, int64_t K,
                            int64_t maxl, int64_t k, int32_t *pos_new_host, int64_t *dsi_new_host, int64_t *l_host);
 
+/* The same selection ON THE DEVICE (neighbors.py:11-183), as the fixed point of a parallel iteration (csrc/balance.hip).  With
+ * rank[lsi[i]] = i, node m is open to cell el exactly when rank[el] <= s[m], s[m] being the maxl-th smallest rank among the cells
+ * that take m (n when fewer than maxl take it).  A ROUND is: select, sort the n * k keys (the caller's sort), thresholds.  The caller
+ * repeats rounds until a select leaves the flag's bit 0 clear and then calls finish; the result is the loop's, integer for integer,
+ * whatever the number of rounds (at most n; a handful on real data).  Device pointers throughout.
+ *
+ * select: dsi (n, K) int32 sight lists with row pitch ldk (elements), as vcy_knn_search leaves them; rank (n) int32; s (n) int32 or
+ *   NULL (every node open: the first round); groups (n) int64 or NULL (the constrained variant: only nodes of el's group); prev (n, k)
+ *   the previous round's sel or NULL (everything counts as changed).  Writes sel (n, k) int32 - the positions in its sight list of the
+ *   first k open entries of every cell, -1 where fewer were found - and keys (n, k) int64: (m << 32) | rank[el] per pick,
+ *   0x7fffffffffffffff for an empty slot.  flag (one int32) is cleared on the stream and then receives bit 0 when any position differs
+ *   from prev, bit 1 when a list entry lies outside 0 .. n-1 (such an entry is skipped).  One wave per cell, stops at the chunk of 64
+ *   entries that holds the k-th pick.
+ * thresholds: from the SORTED keys (ascending as signed 64-bit) s (n) int32 and l (n) int32, the number of cells that take each node.
+ * finish: what vcy_balance_knn_host32 returns, from the final sel and the l of the last thresholds call: dsi_new (n, k+1) int64 (column 0
+ *   the cell itself if the loop's walk meets it, else -1; unfilled slots padded with the cell), pos_new (n, k+1) int32 (-1 for column 0
+ *   and padded slots), l_out (n) int64.
+ * n, K >= k > 0 below 2^31, ldk >= K, maxl > 0.                                                                                  */
+int vcy_balance_select(const int32_t *dsi, int64_t ldk, const int32_t *rank, const int32_t *s, const int64_t *groups,
+                       const int32_t *prev, int32_t *sel, int64_t *keys, int32_t *flag, int64_t n, int64_t K, int64_t k,
+                       vcy_stream stream);
+int vcy_balance_thresholds(const int64_t *sorted_keys, int32_t *s, int32_t *l, int64_t n, int64_t k, int64_t maxl,
+                           vcy_stream stream);
+int vcy_balance_finish(const int32_t *dsi, int64_t ldk, const int32_t *sel, const int32_t *l, int64_t *dsi_new, int32_t *pos_new,
+                       int64_t *l_out, int64_t n, int64_t K, int64_t k, vcy_stream stream);
+
 /* ---------------------------------------------------------------- stage B: gamma fits
  * estimation.fit_slope + _fit1_slope (estimation.py:173-188, 267-279): per gene
  *     gamma = max(0, sum_c x*y / sum_c x*x), NaN if x == 0 everywhere, 0 if y == 0 everywhere;

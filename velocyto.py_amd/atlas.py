@@ -84,14 +84,21 @@ class AtlasPath:
                  c0: int = 0, C_total: Optional[int] = None, k: int = 30, n_neighbors: int = 500, sampled_fraction: float = 0.5,
                  sampling_probs=(0.5, 0.1), block_cells: int = 0, dtype=torch.float32, psc: float = 1e-10, seed: int = 15071990,
                  knn: str = "auto", fit: str = "slope", shift: bool = False, sigma_corr: float = 0.05, expression_scaling: bool = True,
-                 scaling_penalty: float = 1.0):
+                 scaling_penalty: float = 1.0, balanced: bool = False, b_sight: Optional[int] = None, b_maxl: Optional[int] = None,
+                 group_constraint=None):
         """fit: how stage B fits gamma.  "slope" (the default): gamma = max(0, sum xy / sum xx), unweighted, no offset (fit_slope,
         estimation.py:267-279).  "maxmin_diag" (or "default"): velocyto's default fit_gammas(weights="maxmin_diag", fit_offset=True)
         (analysis.py:1179-1257), the recipe of VelocytoLoom.fit_gammas and ShardedLoom.fit_gammas, with the per-gene percentiles
         taken by a streamed exact select (ops.StreamedGeneQuantiles): 9 walks over the pooled blocks in f32, 17 in f64.
         shift: also calculate_embedding_shift (analysis.py:1670-1733, stage E) with sigma_corr, expression_scaling and scaling_penalty
         as there, block by block while the block is in the staging buffers: run() then leaves tp, delta_embedding, scaling and
-        delta_embedding_unscaled of the rank's own cells (see _stage_e); delta_S is never formed."""
+        delta_embedding_unscaled of the rank's own cells (see _stage_e); delta_S is never formed.
+        balanced: pool over the balanced kNN graph (BalancedKNN, neighbors.py:186-357) instead of the plain one.  b_sight and b_maxl
+        default to 8 k and 4 k, the recipe of default_fit_preparation (analysis.py:1942-1977) - NOT knn_imputation's own default of
+        the whole dataset, whose (C, C) sight lists a million cells cannot hold.  Every rank searches the sight lists of its own cells,
+        the int32 lists are all-gathered (C x (b_sight + 1) x 4 bytes per rank) and balanced on every rank's device
+        (ops.balance_knn_positions; its rounds and fallback go to knn_stats).  group_constraint: one label per cell (all C cells, or the
+        rank's own): picks stay inside a cell's group.  With balanced=False the path is bit for bit what it is without these."""
         if fit not in ("slope", "maxmin_diag", "default"):
             raise ValueError(f"AtlasPath: unknown fit={fit!r} (\"slope\", \"maxmin_diag\" or \"default\")")
         self.fit = "slope" if fit == "slope" else "maxmin_diag"
@@ -113,7 +120,9 @@ class AtlasPath:
         emb_full = D.all_gather_rows(embedding.double().contiguous(), self.C)
         # ---- kNN graph of the own cells (analysis.py:1005-1010): nearest-first, self excluded; weights (knn > 0) with diag = 1
         self.knn_stats: Dict[str, float] = {}
-        idx, dist_ = self._knn(pcs_full)
+        if group_constraint is not None and not balanced:
+            raise ValueError("group_constraint is supported only with balanced=True")
+        idx, dist_ = self._balanced_knn(pcs_full, b_sight, b_maxl, group_constraint) if balanced else self._knn(pcs_full)
         conn = (dist_ > 0).to(self.dtype)
         wrow = torch.cat([torch.ones((self.nloc, 1), device=dev, dtype=self.dtype), conn], 1)
         wrow = (wrow / wrow.sum(1, keepdim=True)).contiguous()
@@ -184,6 +193,38 @@ class AtlasPath:
         if self.knn_mode == "pruned" or (self.knn_mode == "auto" and self.C >= PRUNE_FROM):
             return ops.knn_search_pruned(pcs_full, self.k, q0=self.c0, Q=self.nloc, stats=self.knn_stats)
         return ops.knn_search(pcs_full, self.k, include_self=False, q0=self.c0, Q=self.nloc)
+
+    def _balanced_knn(self, pcs_full: torch.Tensor, b_sight, b_maxl, group_constraint):
+        """The balanced graph's rows of the own cells in the form _knn returns: (picks (nloc, k) int32, their distances).  A slot the
+        sight could not fill holds the cell itself at distance 0, which the weights (distance > 0) turn into weight 0."""
+        k, C = self.k, self.C
+        sight = 8 * k if b_sight is None else int(b_sight)
+        maxl = 4 * k if b_maxl is None else int(b_maxl)
+        K = min(sight + 1, C)                                           # the query included, as BalancedKNN.kneighbors searches
+        own = torch.arange(self.c0, self.c1, device=self.dev)
+        if self.knn_mode == "pruned" or (self.knn_mode == "auto" and C >= PRUNE_FROM):
+            # the pruned search excludes the query: the self column (distance 0) goes in front - the same lists, given no duplicate cells
+            idx, dist_ = ops.knn_search_pruned(pcs_full, K - 1, q0=self.c0, Q=self.nloc, stats=self.knn_stats)
+            idx = torch.cat([own.to(torch.int32)[:, None], idx], 1)
+            dist_ = torch.cat([torch.zeros((self.nloc, 1), dtype=dist_.dtype, device=self.dev), dist_], 1)
+        else:
+            idx, dist_ = ops.knn_search(pcs_full, K, include_self=True, q0=self.c0, Q=self.nloc)
+        groups = None
+        if group_constraint is not None:
+            groups = (group_constraint if isinstance(group_constraint, torch.Tensor) else torch.as_tensor(np.asarray(group_constraint))
+                      ).to(self.dev, torch.int64)
+            if groups.numel() == self.nloc and self.nloc != C:
+                groups = D.all_gather_rows(groups.contiguous(), C)
+            if groups.numel() != C:
+                raise ValueError("AtlasPath: group_constraint needs one label per cell (all cells, or the rank's own)")
+        lists = D.all_gather_rows(idx.contiguous(), C)
+        st: Dict[str, float] = {}
+        pos, dsi_new, _ = ops.balance_knn_positions(lists, maxl, k, groups, stats=st)
+        del lists
+        self.knn_stats.update(balance_rounds=st["rounds"], balance_fell_back=st["fell_back"], b_sight=sight, b_maxl=maxl)
+        dsi_own = dsi_new[self.c0:self.c1]
+        dist_own = ops.balance_distances(dist_, pos[self.c0:self.c1], dsi_own, own)
+        return dsi_own[:, 1:].to(torch.int32).contiguous(), dist_own[:, 1:].contiguous()
 
     # ------------------------------------------------------------------ pooling of arbitrary E rows
     def _e_rows_of(self, g: torch.Tensor) -> torch.Tensor:
@@ -481,11 +522,13 @@ def grid_arrows(embedding, delta_embedding, smooth: float = 0.5, steps: Tuple = 
 
 
 def memory_plan(C: int, G: int, nnz_per_cell: float, world: int, block_cells: int, nrndm: int = 250, k: int = 30, count_bytes: int = 1,
-                elem_bytes: int = 4, halo_e: float = 0.1, halo_k: float = 0.25, fit: str = "slope") -> Dict[str, float]:
+                elem_bytes: int = 4, halo_e: float = 0.1, halo_k: float = 0.25, fit: str = "slope", b_sight: int = 0) -> Dict[str, float]:
     """Bytes one rank holds (GB).  halo_e / halo_k: E and count-row halos as fractions of the rank's own cells (measured:
     tools/halo_fraction.py, AtlasPath.n_e_halo / n_count_halo).  fit="maxmin_diag" adds the state of the streamed select at its
     peak (phase 1: three ranks - both of percentile 99.9 and the maximum - of Sx and of Ux): per (rank, gene) a 256-bin uint32
-    histogram, an 8-byte key prefix and a 4-byte rank; it does not grow with the cell count."""
+    histogram, an 8-byte key prefix and a 4-byte rank; it does not grow with the cell count.  b_sight > 0 (AtlasPath(balanced=True)) adds
+    the gathered int32 sight lists of ALL cells, C x (b_sight + 1) x 4 bytes, held while the graph is balanced."""
+    lists = C * (b_sight + 1) * 4 if b_sight > 0 else 0
     select = 0 if fit == "slope" else 2 * 3 * G * (256 * 4 + 8 + 4)
     nloc = math.ceil(C / world)
     ld = ops.padded_ld(G)
@@ -496,7 +539,8 @@ def memory_plan(C: int, G: int, nnz_per_cell: float, world: int, block_cells: in
     return {"cells_per_rank": nloc, "csr_layers_with_halo_GB": gb(csr), "pcs_embedding_replicated_GB": gb(C * 32 * 8),
             "graph_and_neighbour_lists_GB": gb(nloc * (1 + halo_e) * (k + 1) * 8 + nloc * nrndm * 4), "block_Sx_Ux_GB": gb(dense_block),
             "corr_rows_GB": gb(nloc * nrndm * elem_bytes), "kNN_workspace_GB": gb(8192 * C * 4), "fit_select_histograms_GB": gb(select),
-            "total_GB": gb(csr + C * 32 * 8 + dense_block + nloc * nrndm * (4 + elem_bytes) + 8192 * C * 4 + select)}
+            "balanced_sight_lists_GB": gb(lists),
+            "total_GB": gb(csr + C * 32 * 8 + dense_block + nloc * nrndm * (4 + elem_bytes) + 8192 * C * 4 + select + lists)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -135,8 +135,14 @@ class BalancedKNN:
     """neighbors.py:186-357: greedy in-degree-capped kNN graph with a scikit-learn-like API."""
 
     def __init__(self, k: int = 50, sight_k: int = 100, maxl: int = 200, constraint: np.ndarray = None, mode: str = "distance",
-                 metric: str = "euclidean", n_jobs: int = 4) -> None:
+                 metric: str = "euclidean", n_jobs: int = 4, balance: str = "host") -> None:
+        """balance: where the greedy selection of kneighbors on the fitted points runs.  "host" (the default): the sequential loop on an
+        int32 host copy of the sight lists (ops.balance_knn_device_lists).  "device": the same integers as the fixed point of a parallel
+        iteration on the device (ops.balance_knn_device), no host copy of the lists; `balance_stats` then holds its rounds."""
+        if balance not in ("host", "device"):
+            raise ValueError(f"BalancedKNN: unknown balance={balance!r} (\"host\" or \"device\")")
         self.k, self.sight_k, self.maxl, self.mode, self.metric, self.n_jobs = k, sight_k, maxl, mode, metric, n_jobs
+        self.balance, self.balance_stats = balance, None
         self.dist_new = self.dsi_new = self.l = None
         self.bknn = None
         self.constraint = constraint
@@ -193,7 +199,12 @@ class BalancedKNN:
             self.__dict__.pop("dsi", None); self.__dict__.pop("dist", None)
             logging.debug(f"Using the initialization network to find a {self.k}-NN graph with maximum connectivity of {self.maxl}")
             groups = None if self.constraint is None else np.asarray(self.constraint).astype("int64")
-            self.dist_new, self.dsi_new, self.l = ops.balance_knn_device_lists(idx, dist, self.maxl, self.k, groups)
+            if self.balance == "device":
+                self.balance_stats = {}
+                res = ops.balance_knn_device(idx, dist, self.maxl, self.k, groups, stats=self.balance_stats)
+                self.dist_new, self.dsi_new, self.l = (t.cpu().numpy() for t in res)
+            else:
+                self.dist_new, self.dsi_new, self.l = ops.balance_knn_device_lists(idx, dist, self.maxl, self.k, groups)
             if mode == "connectivity":
                 self.dist = np.ones((idx.shape[0], idx.shape[1]), dtype=np.int64)
                 self.dist[:, 0] = 0

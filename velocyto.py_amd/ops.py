@@ -1287,6 +1287,132 @@ def balance_knn_host(dsi: np.ndarray, dist: Optional[np.ndarray], lsi: np.ndarra
     return dist_new, dsi_new, l
 
 
+def _balance_order(idx: torch.Tensor) -> torch.Tensor:
+    """knn_balance's processing order (neighbors.py:172-174) of (C, K) sight lists on the device: l0 = bincount(dsi),
+    lsi = np.argsort(l0, kind="mergesort")[::-1] - stable ascending, reversed, so ties come out by DEscending cell number."""
+    l0 = torch.bincount(idx.reshape(-1).long(), minlength=idx.shape[0])
+    if l0.numel() > idx.shape[0]:
+        raise ValueError("balance_knn: dsi entry out of range")
+    return torch.flip(torch.sort(l0, stable=True).indices, [0])
+
+
+def _balance_host32(idx: torch.Tensor, lsi: torch.Tensor, groups: Optional[np.ndarray], maxl: int, k: int
+                    ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The sequential loop (vcy_balance_knn_host32) on an int32 host copy of the device lists: (pos_new, dsi_new, l) as numpy."""
+    C, K = idx.shape
+    lsi = lsi.cpu().numpy().astype(np.int64)
+    host = np.ascontiguousarray(idx.cpu().numpy())             # int32, the only big host array
+    g = None if groups is None else np.ascontiguousarray(groups, dtype=np.int64)
+    pos = np.empty((C, k + 1), dtype=np.int32)
+    dsi_new = np.empty((C, k + 1), dtype=np.int64)
+    l = np.empty(C, dtype=np.int64)
+    _lib.check(_lib.lib().vcy_balance_knn_host32(host.ctypes.data, lsi.ctypes.data, None if g is None else g.ctypes.data, C, K, int(maxl), int(k),
+                                                 pos.ctypes.data, dsi_new.ctypes.data, l.ctypes.data), "balance_knn32")
+    return pos, dsi_new, l
+
+
+def balance_workspace_bytes(n: int, k: int) -> int:
+    """Bytes of the workspace of balance_knn_device: the keys (n, k) int64, two selections (n, k) int32, s and l (n) int32, the flag."""
+    return 16 * n * k + 8 * n + 8
+
+
+def balance_knn_positions(idx: torch.Tensor, maxl: int, k: int, groups=None, max_rounds: int = 64, stats: Optional[dict] = None,
+                          workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The selection of balance_knn_device without the distances: DEVICE tensors (pos_new (C, k+1) int32, dsi_new (C, k+1) int64,
+    l (C) int64) as vcy_balance_knn_host32 writes them - pos_new the position of every pick in its cell's sight list, -1 for column
+    0 and padded slots.  A caller that holds the distances of some rows only (a rank of a cell-sharded run) gathers them with
+    balance_distances."""
+    C, K = idx.shape
+    k, maxl = int(k), int(maxl)
+    if K < k:
+        raise AssertionError("sight needs to be bigger than k")
+    if idx.dtype != torch.int32 or not idx.is_cuda or idx.stride(1) != 1 or idx.stride(0) < K:
+        raise ValueError("balance_knn_device: idx must be a (C, K) int32 device tensor with unit column stride")
+    dev = idx.device
+    g = None if groups is None else torch.as_tensor(np.asarray(groups).astype("int64") if not isinstance(groups, torch.Tensor) else groups
+                                                    ).to(dev, torch.int64).contiguous()
+    if g is not None and g.numel() != C:
+        raise ValueError("balance_knn_device: one group per cell")
+    lsi = _balance_order(idx)
+    rank = torch.empty(C, dtype=torch.int32, device=dev)
+    rank[lsi] = torch.arange(C, dtype=torch.int32, device=dev)
+    nk = C * k
+    need = balance_workspace_bytes(C, k)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or ws.device != dev or ws.numel() < need or not ws.is_contiguous() or ws.data_ptr() % 8:
+        raise ValueError(f"balance_knn_device: workspace must hold {need} contiguous, 8-byte aligned uint8 on {dev}")
+    keys = ws[:8 * nk].view(torch.int64)
+    sel = [ws[8 * nk:12 * nk].view(torch.int32), ws[12 * nk:16 * nk].view(torch.int32)]
+    s = ws[16 * nk:16 * nk + 4 * C].view(torch.int32)
+    l32 = ws[16 * nk + 4 * C:16 * nk + 8 * C].view(torch.int32)
+    flag = ws[16 * nk + 8 * C:16 * nk + 8 * C + 4].view(torch.int32)
+    L = _lib.lib()
+    ldk = idx.stride(0)
+    rounds, fell_back, prev, first = 0, False, None, True
+    while True:
+        cur = sel[rounds & 1]
+        _lib.check(L.vcy_balance_select(idx.data_ptr(), ldk, rank.data_ptr(), None if first else s.data_ptr(), _p(g), _p(prev), cur.data_ptr(),
+                                        keys.data_ptr(), flag.data_ptr(), C, K, k, _stream()), "balance_select")
+        rounds += 1
+        bits = int(flag.item())                                # the round's one synchronisation
+        if bits & 2:
+            raise ValueError("balance_knn_device: dsi entry out of range")
+        if not bits & 1:
+            break
+        if rounds >= int(max_rounds):
+            fell_back = True
+            break
+        sorted_keys = torch.sort(keys).values                  # index plumbing, as markov_csr's argsort; real keys are distinct
+        _lib.check(L.vcy_balance_thresholds(sorted_keys.data_ptr(), s.data_ptr(), l32.data_ptr(), C, k, maxl, _stream()),
+                   "balance_thresholds")
+        prev, first = cur, False
+    if stats is not None:
+        stats.update(rounds=rounds, fell_back=fell_back)
+    if fell_back:
+        pos_h, dsi_h, l_h = _balance_host32(idx, lsi, None if g is None else g.cpu().numpy(), maxl, k)
+        pos, dsi_new, l = torch.from_numpy(pos_h).to(dev), torch.from_numpy(dsi_h).to(dev), torch.from_numpy(l_h).to(dev)
+    else:
+        pos = torch.empty((C, k + 1), dtype=torch.int32, device=dev)
+        dsi_new = torch.empty((C, k + 1), dtype=torch.int64, device=dev)
+        l = torch.empty(C, dtype=torch.int64, device=dev)
+        _lib.check(L.vcy_balance_finish(idx.data_ptr(), ldk, cur.data_ptr(), l32.data_ptr(), dsi_new.data_ptr(), pos.data_ptr(), l.data_ptr(),
+                                        C, K, k, _stream()), "balance_finish")
+    return pos, dsi_new, l
+
+
+def balance_distances(dist: torch.Tensor, pos: torch.Tensor, dsi_new: torch.Tensor, cells: torch.Tensor) -> torch.Tensor:
+    """dist_new of knn_balance for the rows `cells` (their numbers, int64): `dist` (rows, K) their sight distances, `pos` / `dsi_new`
+    their rows of balance_knn_positions.  A pick carries its distance, a padded slot dist[el, 0] (neighbors.py:65-69), column 0 the 0
+    it is initialised with."""
+    pd = pos.long()
+    got = torch.gather(dist, 1, pd.clamp(min=0))
+    pad = (dsi_new == cells[:, None]) & (pd < 0)
+    got = torch.where(pd >= 0, got, torch.where(pad, dist[:, :1].expand_as(got), torch.zeros_like(got)))
+    got[:, 0] = 0.0
+    return got
+
+
+def balance_knn_device(idx: torch.Tensor, dist: Optional[torch.Tensor], maxl: int, k: int, groups=None, max_rounds: int = 64,
+                       stats: Optional[dict] = None, workspace: Optional[torch.Tensor] = None
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """knn_balance (neighbors.py:143-183) without the host: the greedy loop as the fixed point of a parallel iteration
+    (csrc/balance.hip).  `idx` (C, K) int32 sight lists on the device (rows may carry a pitch), `dist` (C, K) fp64 or None, `groups`
+    (C) integers or None.  Returns DEVICE tensors (dist_new (C, k+1) fp64, dsi_new (C, k+1) int64, l (C) int64) holding what
+    balance_knn_device_lists returns as numpy, bit for bit.
+
+    A round is one walk of every cell over its list (vcy_balance_select), one sort of the C * k keys and the thresholds
+    (vcy_balance_thresholds); the host reads the 4-byte change flag once per round - the only synchronisation.  The cells of rank
+    < t are final after round t, so the rounds end (at most C of them, a handful on real data) and end at the loop's
+    result.  `max_rounds` guards the cost, not the result: if the selections still change after that many rounds the same lists go
+    through the host loop (vcy_balance_knn_host32) instead.  `stats` receives `rounds` and `fell_back`; `workspace` (optional):
+    balance_workspace_bytes(C, k) bytes of uint8 on idx's device, contents irrelevant."""
+    pos, dsi_new, l = balance_knn_positions(idx, maxl, k, groups, max_rounds, stats, workspace)
+    C = idx.shape[0]
+    if dist is None:
+        return torch.ones((C, int(k) + 1), dtype=torch.float64, device=idx.device), dsi_new, l     # neighbors.py:176-183 without distances
+    return balance_distances(dist, pos, dsi_new, torch.arange(C, device=idx.device)), dsi_new, l
+
+
 def balance_knn_device_lists(idx: torch.Tensor, dist: torch.Tensor, maxl: int, k: int, groups: Optional[np.ndarray] = None
                              ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """knn_balance (neighbors.py:143-183) on sight lists that STAY where the search left them: `idx` (C, K) int32 and `dist`
@@ -1297,17 +1423,7 @@ def balance_knn_device_lists(idx: torch.Tensor, dist: torch.Tensor, maxl: int, k
     C, K = idx.shape
     if K < k:
         raise AssertionError("sight needs to be bigger than k")
-    l0 = torch.bincount(idx.reshape(-1).long(), minlength=C)
-    # np.argsort(l, kind="mergesort")[::-1]: stable ascending, reversed (ties come out by DEscending cell number)
-    lsi = torch.flip(torch.sort(l0, stable=True).indices, [0]).cpu().numpy().astype(np.int64)
-    host = idx.cpu().numpy()                                   # int32, the only big host array
-    g = None if groups is None else np.ascontiguousarray(groups, dtype=np.int64)
-    pos = np.empty((C, k + 1), dtype=np.int32)
-    dsi_new = np.empty((C, k + 1), dtype=np.int64)
-    l = np.empty(C, dtype=np.int64)
-    _lib.check(_lib.lib().vcy_balance_knn_host32(host.ctypes.data, lsi.ctypes.data, None if g is None else g.ctypes.data, C, K, int(maxl), int(k),
-                                                 pos.ctypes.data, dsi_new.ctypes.data, l.ctypes.data), "balance_knn32")
-    del host
+    pos, dsi_new, l = _balance_host32(idx, _balance_order(idx), groups, maxl, k)
     pd = torch.from_numpy(pos).to(idx.device).long()
     got = torch.gather(dist, 1, pd.clamp(min=0))
     pad = torch.from_numpy(dsi_new == np.arange(C)[:, None]).to(idx.device) & (pd < 0)     # padded slots carry dist[el, 0] (neighbors.py:65-69)

@@ -47,7 +47,7 @@ class ShardedLoom:
     the file in blocks of 8 192 cells and keeps its columns, so each reads about the whole file once - host I/O, nothing is
     exchanged.)
 
-    Not covered (NotImplementedError): balanced kNN, duplicate cells in the kNN space (a distance of 0: the facade then builds the
+    Not covered (NotImplementedError): duplicate cells in the kNN space (a distance of 0: the facade then builds the
     graph through scipy), the non-default weight modes of fit_gammas, knn_random=False, transform="logratio", hidim="pcs"."""
 
     def __init__(self, loom_path: Optional[str] = None, pcs=None, ts=None, *, dtype=None, group=None, layers=None) -> None:
@@ -181,31 +181,37 @@ class ShardedLoom:
                        maximum: bool = False, size_norm: bool = True, balanced: bool = False, b_sight: int = None, b_maxl: int = None,
                        group_constraint=None, n_jobs: int = 8) -> None:
         """analysis.py:933-1023: each rank searches the neighbours of its own cells, fetches the halo rows its graph references and
-        pools its rows with the facade's kernels."""
+        pools its rows with the facade's kernels.
+
+        balanced=True (BalancedKNN, neighbors.py:186-357, with the facade's defaults b_sight = max(8 k, C - 1) and b_maxl =
+        max(4 k, C - 1)): each rank searches the sight lists of its own cells, the int32 lists are all-gathered in the user's cell
+        numbers (the balancing breaks ties by cell number) and EVERY rank balances the whole graph on its device
+        (ops.balance_knn_positions: integer work, the same result everywhere, nothing to broadcast); the distances stay with the rank
+        that searched them.  The gathered lists take C x (b_sight + 1) x 4 bytes on every rank: C x C x 4 at the whole-dataset
+        default (10 GB at 50 000 cells) - pass b_sight for more cells than that holds.  group_constraint: "clusters" (self.cluster_ix)
+        or one label per cell in the user's order.  Rounds and fallback of the balancing: self.knn_stats."""
         t0 = time.perf_counter()
-        if balanced:
-            raise NotImplementedError("balanced=True: the balancing is a sequential host loop over all cells")
-        if not pca_space or metric != "euclidean" or diag == 0 or not size_norm or group_constraint is not None:
-            raise NotImplementedError("ShardedLoom.knn_imputation covers the PCA space, the euclidean metric, diag != 0 and size_norm=True")
+        if not pca_space or metric != "euclidean" or diag == 0 or not size_norm or (group_constraint is not None and not balanced):
+            raise NotImplementedError("ShardedLoom.knn_imputation covers the PCA space, the euclidean metric, diag != 0 and size_norm=True "
+                                      "(group_constraint with balanced=True only)")
         C = self.C
         if k is None:
             k = int(C * 0.025)
         space = torch.from_numpy(np.ascontiguousarray(self.pcs[:, :n_pca_dims])).to(self.dev)
         space_run = space.index_select(0, self._user).contiguous()
-        idx, dist = ops.knn_search(space_run, k, include_self=False, q0=self.c0, Q=self.nloc)
-        pos = torch.tensor([1.0 if bool((dist > 0).all()) else 0.0], device=self.dev)
-        self._reduce_min(pos)
-        if float(pos) < 0.5:
-            raise NotImplementedError("knn_imputation: cells at distance 0 (duplicates) need the scipy graph of the facade")
-        # the facade's rows (weight_rows_from_sorted_knn) in user numbers: the cell itself and its k neighbours, sorted by user number
-        nb_user = self._user[idx.long()].to(torch.int32)
-        me = self._mine.to(torch.int32)[:, None]
-        cols = torch.cat([me, nb_user], 1)
-        vals = torch.ones((self.nloc, k + 1), dtype=torch.float64, device=self.dev)
-        vals[:, 0] = float(diag)
-        vals = vals * (1.0 / (np.float64(k) + np.float64(diag)))
+        if balanced:
+            cols, vals = self._balanced_rows(space_run, int(k), diag, b_sight, b_maxl, group_constraint)
+        else:
+            idx, dist = ops.knn_search(space_run, k, include_self=False, q0=self.c0, Q=self.nloc)
+            self._refuse_duplicates(bool((dist > 0).all()))
+            # the facade's rows (weight_rows_from_sorted_knn) in user numbers: the cell itself and its k neighbours, sorted by user number
+            nb_user = self._user[idx.long()].to(torch.int32)
+            cols = torch.cat([self._mine.to(torch.int32)[:, None], nb_user], 1)
+            vals = torch.ones((self.nloc, k + 1), dtype=torch.float64, device=self.dev)
+            vals[:, 0] = float(diag)
+            vals = vals * (1.0 / (np.float64(k) + np.float64(diag)))
+        self._knn_user = torch.sort(cols[:, 1:], dim=1).values           # (the facade's idx_s, user numbers)
         cols, vals = ops.canonical_graph_rows(cols, vals)
-        self._knn_user = torch.sort(nb_user, dim=1).values               # (the facade's idx_s, user numbers)
         rows_run = self._inv[cols.long()]                                # run order
         need = torch.zeros(C, dtype=torch.bool, device=self.dev)
         need[rows_run.reshape(-1)] = True
@@ -234,6 +240,42 @@ class ShardedLoom:
         for n, m in (("Sx", Sx), ("Ux", Ux), ("Sx_sz", Sx), ("Ux_sz", Ux)):
             self._m[n] = m
         self._timed("knn_imputation", t0)
+
+    def _refuse_duplicates(self, fine: bool) -> None:
+        """Collective: every rank raises if any rank found cells at distance 0."""
+        pos = torch.tensor([1.0 if fine else 0.0], device=self.dev)
+        self._reduce_min(pos)
+        if float(pos) < 0.5:
+            raise NotImplementedError("knn_imputation: cells at distance 0 (duplicates) need the scipy graph of the facade")
+
+    def _balanced_rows(self, space_run: torch.Tensor, k: int, diag: float, b_sight, b_maxl, group_constraint):
+        """The rank's rows of the balanced graph in user numbers: (cols (nloc, k + 1) int32 - the cell itself, then its picks, a slot the
+        sight could not fill holding the cell again - and their weights): what (knn > 0), setdiag(diag) and connectivity_to_weights
+        (analysis.py:1006-1010) make of BalancedKNN's graph - weight (distance > 0) per pick, diag for the cell, times the reciprocal
+        of the row sum; a padded slot has distance 0 and weight 0."""
+        C = self.C
+        sight = int(np.maximum(int(k * 8), C - 1)) if b_sight is None else int(b_sight)
+        maxl = int(np.maximum(int(k * 4), C - 1)) if b_maxl is None else int(b_maxl)
+        K = min(sight + 1, C)                                           # the query included, as BalancedKNN.kneighbors searches
+        idx, dist = ops.knn_search(space_run, K, include_self=True, q0=self.c0, Q=self.nloc)
+        own_first = idx[:, 0] == torch.arange(self.c0, self.c1, device=self.dev, dtype=idx.dtype)
+        self._refuse_duplicates(bool(own_first.all()) and bool((dist[:, 1:] > 0).all()))
+        lists = self._gather_cells(self._user[idx.long()].to(torch.int32))     # (C, K) int32: user numbers, rows in the user's order
+        groups = None
+        if group_constraint is not None:
+            groups = np.array(self.cluster_ix) if isinstance(group_constraint, str) and group_constraint == "clusters" else np.asarray(group_constraint)
+        self.knn_stats = {}
+        pos, dsi_new, _ = ops.balance_knn_positions(lists, maxl, k, groups, stats=self.knn_stats)
+        del lists
+        mine = self._mine
+        dsi_own = dsi_new[mine]
+        dist_own = ops.balance_distances(dist, pos[mine], dsi_own, mine)
+        conn = (dist_own[:, 1:] > 0)
+        # 1 / (picks + diag) for every possible number of picks, divided on the host as scipy divides (one IEEE division each)
+        scale = torch.from_numpy(1.0 / (np.arange(k + 1, dtype=np.float64) + np.float64(diag))).to(self.dev)
+        vals = torch.cat([torch.full((self.nloc, 1), float(diag), dtype=torch.float64, device=self.dev), conn.double()], 1)
+        vals = vals * scale[conn.sum(1)][:, None]
+        return dsi_own.to(torch.int32), vals
 
     # ------------------------------------------------------------------ stage B
     def _slices(self) -> D.GeneSlices:
