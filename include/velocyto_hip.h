@@ -658,6 +658,35 @@ int vcy_tsne_step(const float *Y, float *Y_out, const int64_t *indptr, const int
                   float *gains, double *stats, void *workspace, int64_t N, int n_components, double momentum, double learning_rate,
                   double min_gain, int compute_error, vcy_stream stream);
 
+/* The same objective with the repulsion of scikit-learn's Barnes-Hut rule, n_components == 2 only (anything else:
+ * VCY_ERR_UNSUPPORTED): a complete quadtree of `depth` levels below the root (1 .. 11; vcy_tsne_tree_depth(N): the automatic
+ * depth) over the bounding square of Y, rebuilt at every evaluation; a node of level l is accepted for a target iff
+ * f32((side 2^-l)^2) < f32(angle^2) (dx dx + dy dy) in separately rounded f32 against the node's centre of mass, 0 <= angle <= 1
+ * (angle == 0: the exact sum); a leaf that is not accepted is summed point by point, the target itself left out.  Per evaluation:
+ * vcy_tsne_tree_keys writes the box into the workspace and every point's leaf-cell Morton key (x in the even bits) into keys (N)
+ * int32; the caller sorts them (order (N) int64 = the stable argsort, sorted_keys = keys[order]) and passes both, with the SAME
+ * workspace, to one of
+ *   vcy_tsne_tree_repulsion: rep (N, 3) f64 = the force x, y and sum_j w_ij of every point (by its original number), Z (1) f64,
+ *     visits (N, 2) int32 or NULL = accepted nodes and directly summed points per target;
+ *   vcy_tsne_tree_gradient / vcy_tsne_tree_step: vcy_tsne_gradient / vcy_tsne_step with that repulsion.
+ * Deterministic (no atomics; every sum in a fixed order).  Workspace, vcy_tsne_tree_workspace_bytes(N, depth) bytes (0: arguments
+ * out of range), in 128-byte aligned sections: head (lo x, lo y, side, 2^depth / side f64; 12 f32 = f32((side 2^-l)^2); padding to
+ * 128 bytes) | 256 x 16 bytes of box partials | nodes, 16 bytes each {int32 count, f32 com x, f32 com y, 0}, level l at node
+ * (4^l - 1) / 3 in Morton order, (4^(depth+1) - 1) / 3 in all | start int32 (4^depth + 1) | sorted positions (N, 2) f32 |
+ * part (3, N) f64 | per-workgroup partials. */
+int vcy_tsne_tree_depth(int64_t N);
+size_t vcy_tsne_tree_workspace_bytes(int64_t N, int depth);
+int vcy_tsne_tree_keys(const float *Y, int32_t *keys, void *workspace, int64_t N, int depth, vcy_stream stream);
+int vcy_tsne_tree_repulsion(const float *Y, const int64_t *order, const int32_t *sorted_keys, double *rep, double *Z, int32_t *visits,
+                            void *workspace, int64_t N, int depth, double angle, vcy_stream stream);
+int vcy_tsne_tree_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
+                           const int32_t *sorted_keys, float *grad, double *stats, void *workspace, int64_t N, int n_components,
+                           int depth, double angle, int compute_error, vcy_stream stream);
+int vcy_tsne_tree_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval,
+                       const int64_t *order, const int32_t *sorted_keys, double *update, float *gains, double *stats, void *workspace,
+                       int64_t N, int n_components, int depth, double angle, double momentum, double learning_rate, double min_gain,
+                       int compute_error, vcy_stream stream);
+
 /* ---------------------------------------------------------------- upstream caller: PCA straight from CSR count layers
  * perform_PCA on S_norm = log2(S_sz + pcount) (analysis.py:549-551, 678-700) where the layer only exists as CSR counts (the atlas
  * path; the reference forms S_norm dense in float64).  A stored count c stands for x = log2(c * s + pcount) - log2(pcount), computed

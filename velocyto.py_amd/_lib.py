@@ -94,6 +94,13 @@ SIGNATURES = {
     "vcy_tsne_perplexity": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp]),
     "vcy_tsne_gradient": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "vcy_tsne_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp]),
+    "vcy_tsne_tree_depth": (c_int, [c_i64]),
+    "vcy_tsne_tree_workspace_bytes": (c_sz, [c_i64, c_int]),
+    "vcy_tsne_tree_keys": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
+    "vcy_tsne_tree_repulsion": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_dbl, c_vp]),
+    "vcy_tsne_tree_gradient": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_dbl, c_int, c_vp]),
+    "vcy_tsne_tree_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_dbl,
+                                   c_dbl, c_dbl, c_dbl, c_int, c_vp]),
     "vcy_csr_spmm_chunk": (c_i64, []),
     "vcy_csr_spmm_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_csr_lognorm_spmm": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_dbl, c_int, c_int, c_vp]),

@@ -15,6 +15,8 @@
 //                        rows of P (+ the error terms), the gradient, and with STEP the gains / momentum / position update;
 //                        per-workgroup partials of the error and of |grad|^2.
 //   k_tsne_stats         KL and |grad|^2 from the partials (one workgroup), at the iterations whose error is asked for.
+//   k_tree_*, k_tsne_tree_repulsion  (vcy_tsne_tree_*, D = 2, opt-in) the repulsion by scikit-learn's Barnes-Hut acceptance rule with the
+//                        caller's angle on a complete quadtree; it fills the same partials, so k_tsne_step / k_tsne_stats are shared.
 #include "common.h"
 #include <float.h>
 
@@ -311,6 +313,386 @@ static int tsne_dispatch(const float *Y, float *Yout, const int64_t *indptr, con
     }
 }
 
+// ---------------------------------------------------------------- tree repulsion (D = 2)
+// scikit-learn's Barnes-Hut acceptance rule (max_width^2 / dist^2 < angle^2, per target) on a complete quadtree of `depth`
+// levels below the root, rebuilt at every evaluation; DESIGN.md section 9 has the contract.  Per evaluation:
+//   k_tree_box, k_tree_keys   the bounding box (min / max: order-free), and every point's Morton key of its leaf cell
+//                             (f64, separately rounded; clamped before the integer conversion)
+//   [the caller sorts the keys: order = stable argsort, plumbing]
+//   k_tree_start, k_tree_gather  start[cell] = first sorted position of the cell (binary search), positions in sorted order
+//   k_tree_up<LEAF>           f64 sums of the leaf cells (points in sorted order) and of 4 levels above them per launch
+//                             (children 0, 1, 2, 3 in that order): no atomics
+//   k_tree_finalize           node record {count, com.x, com.y} in place of the f64 sums (count comes from start[])
+//   k_tsne_tree_repulsion     one wave per 64 consecutive sorted targets, one wave-uniform depth-first walk of the implicit tree
+// Workspace: TreeHead (128 bytes) | box partials | nodes 16 bytes x (4^(depth+1) - 1) / 3, level l at (4^l - 1) / 3 in Morton
+// order | start int32 x (4^depth + 1) | sorted positions | part (3, N) f64 | zpart | blk: what k_tsne_step reads.
+constexpr int TREE_MAX_DEPTH = 11;
+constexpr int TREE_BOX_BLOCKS = 256;               // workgroups of the min / max pass
+constexpr int TREE_RUN = 256;                      // f32 terms added between two f64 carries (as TSNE_TILE in the exact kernel)
+
+struct TreeHead {
+    double lo[2], side, scale;                     // box corner, larger extent, 2^depth / side (0 when side is 0 or not finite)
+    float w2[TREE_MAX_DEPTH + 1];                  // f32((side 2^-l)^2)
+    float pad[12];
+};
+static_assert(sizeof(TreeHead) == 128, "TreeHead");
+
+struct TreePlan {
+    int L, nbx, tb, nb;
+    int64_t cells, nodes;
+    size_t boxp_off, node_off, start_off, ysort_off, part_off, zpart_off, blk_off, bytes;
+};
+static size_t tree_align(size_t b) { return (b + 127) / 128 * 128; }
+static TreePlan tree_plan(int64_t N, int L)
+{
+    TreePlan p;
+    p.L = L;
+    p.cells = 1ll << (2 * L);
+    p.nodes = ((1ll << (2 * L + 2)) - 1) / 3;
+    p.nbx = (int)((N + TSNE_TPB - 1) / TSNE_TPB < TREE_BOX_BLOCKS ? (N + TSNE_TPB - 1) / TSNE_TPB : TREE_BOX_BLOCKS);
+    p.tb = p.nb = (int)((N + TSNE_TPB - 1) / TSNE_TPB);
+    p.boxp_off = sizeof(TreeHead);
+    p.node_off = p.boxp_off + tree_align(sizeof(float4) * TREE_BOX_BLOCKS);
+    p.start_off = p.node_off + tree_align(16 * (size_t)p.nodes);
+    p.ysort_off = p.start_off + tree_align(sizeof(int) * (size_t)(p.cells + 1));
+    p.part_off = p.ysort_off + tree_align(sizeof(float2) * (size_t)N);
+    p.zpart_off = p.part_off + tree_align(sizeof(double) * 3 * (size_t)N);
+    p.blk_off = p.zpart_off + tree_align(sizeof(double) * (size_t)p.tb);
+    p.bytes = p.blk_off + tree_align(sizeof(double) * 2 * (size_t)p.nb);
+    return p;
+}
+
+__device__ __forceinline__ unsigned tree_level_offset(int l) { return 0x55555555u & ((1u << (2 * l)) - 1u); }   // (4^l - 1) / 3
+__device__ __forceinline__ unsigned tree_spread(unsigned x)
+{
+    x &= 0xffffu;
+    x = (x | (x << 8)) & 0x00ff00ffu;
+    x = (x | (x << 4)) & 0x0f0f0f0fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    return (x | (x << 1)) & 0x55555555u;
+}
+
+// (min x, min y, max x, max y) over the workgroup, valid in every thread; fminf / fmaxf drop a NaN operand
+__device__ __forceinline__ float4 tree_block_box(float4 b, float4 *s_box)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        b.x = fminf(b.x, __shfl_xor(b.x, off, 64));
+        b.y = fminf(b.y, __shfl_xor(b.y, off, 64));
+        b.z = fmaxf(b.z, __shfl_xor(b.z, off, 64));
+        b.w = fmaxf(b.w, __shfl_xor(b.w, off, 64));
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_box[threadIdx.x >> 6] = b;
+    __syncthreads();
+    b = s_box[0];
+    for (int i = 1; i < TSNE_TPB / VCY_WAVE; ++i) {
+        b.x = fminf(b.x, s_box[i].x);
+        b.y = fminf(b.y, s_box[i].y);
+        b.z = fmaxf(b.z, s_box[i].z);
+        b.w = fmaxf(b.w, s_box[i].w);
+    }
+    return b;
+}
+
+__global__ __launch_bounds__(TSNE_TPB) void k_tree_box(const float2 *__restrict__ Y, float4 *__restrict__ boxp, int N)
+{
+    __shared__ float4 s_box[TSNE_TPB / VCY_WAVE];
+    float4 b = make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
+    for (int i = blockIdx.x * TSNE_TPB + threadIdx.x; i < N; i += gridDim.x * TSNE_TPB) {
+        const float2 y = Y[i];
+        b.x = fminf(b.x, y.x);
+        b.y = fminf(b.y, y.y);
+        b.z = fmaxf(b.z, y.x);
+        b.w = fmaxf(b.w, y.y);
+    }
+    b = tree_block_box(b, s_box);
+    if (threadIdx.x == 0) boxp[blockIdx.x] = b;
+}
+
+// cell coordinate min(2^L - 1, floor((y - lo) scale)), clamped before the conversion; NaN and negative products give 0
+__device__ __forceinline__ unsigned tree_cell(float y, double lo, double scale, int L)
+{
+    const double t = __dmul_rn(__dsub_rn((double)y, lo), scale);
+    const double top = (double)((1 << L) - 1);
+    if (!(t >= 0.0)) return 0u;
+    return t >= top ? (unsigned)((1 << L) - 1) : (unsigned)(int)floor(t);
+}
+
+__global__ __launch_bounds__(TSNE_TPB) void k_tree_keys(const float2 *__restrict__ Y, const float4 *__restrict__ boxp, int nbx,
+                                                        TreeHead *__restrict__ head, int32_t *__restrict__ keys, int N, int L)
+{
+    __shared__ float4 s_box[TSNE_TPB / VCY_WAVE];
+    float4 b = (int)threadIdx.x < nbx ? boxp[threadIdx.x] : make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
+    b = tree_block_box(b, s_box);                                      // every workgroup: the same box
+    const double lox = (double)b.x, loy = (double)b.y;
+    const double side = fmax(__dsub_rn((double)b.z, lox), __dsub_rn((double)b.w, loy));
+    const double scale = (side > 0.0 && side < INFINITY) ? __ddiv_rn((double)(1 << L), side) : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        head->lo[0] = lox; head->lo[1] = loy; head->side = side; head->scale = scale;
+        for (int l = 0; l <= TREE_MAX_DEPTH; ++l) {
+            const double s = __dmul_rn(side, 1.0 / (double)(1 << l));
+            head->w2[l] = (float)__dmul_rn(s, s);
+        }
+        for (int l = 0; l < 12; ++l) head->pad[l] = 0.0f;
+    }
+    const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (i < N) {
+        const float2 y = Y[i];
+        keys[i] = (int32_t)(tree_spread(tree_cell(y.x, lox, scale, L)) | (tree_spread(tree_cell(y.y, loy, scale, L)) << 1));
+    }
+}
+
+// start[c] = number of sorted keys below c, c = 0 .. cells: in [0, N] whatever the keys hold
+__global__ __launch_bounds__(TSNE_TPB) void k_tree_start(const int32_t *__restrict__ skeys, int *__restrict__ start, int N, unsigned cells)
+{
+    const unsigned c = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (c > cells) return;
+    int lo = 0, hi = N;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if ((long long)skeys[mid] < (long long)c) lo = mid + 1; else hi = mid;
+    }
+    start[c] = lo;
+}
+
+__global__ __launch_bounds__(TSNE_TPB) void k_tree_gather(const float2 *__restrict__ Y, const int64_t *__restrict__ order, float2 *__restrict__ ysort, int N)
+{
+    const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (i >= N) return;
+    const int64_t o = order[i];
+    ysort[i] = Y[(uint64_t)o < (uint64_t)N ? o : 0];
+}
+
+// Levels l0, l0 - 1, .., l0 - 4 (down to the root): thread t of a workgroup owns node 256 block + t of level l0, then the
+// first 64, 16, 4, 1 threads own the workgroup's nodes one, two, three, four levels up.
+template <bool LEAF>
+__global__ __launch_bounds__(TSNE_TPB) void k_tree_up(double2 *nsum, const int *__restrict__ start, const float2 *__restrict__ ysort, int N, int l0)
+{
+    const unsigned base = blockIdx.x * TSNE_TPB, m = base + threadIdx.x;
+    if (m < (1u << (2 * l0))) {
+        double sx = 0.0, sy = 0.0;
+        if constexpr (LEAF) {
+            const int b = max(start[m], 0), e = min(start[m + 1], N);
+#pragma unroll 8
+            for (int j = b; j < e; ++j) {                              // the loads run ahead, the sums stay in order
+                const float2 y = ysort[j];
+                sx += (double)y.x;
+                sy += (double)y.y;
+            }
+        } else {
+            const double2 *ch = nsum + tree_level_offset(l0 + 1) + 4u * m;
+            for (int c = 0; c < 4; ++c) { sx += ch[c].x; sy += ch[c].y; }
+        }
+        nsum[tree_level_offset(l0) + m] = make_double2(sx, sy);
+    }
+    for (int s = 1; s <= 4 && l0 - s >= 0; ++s) {
+        __syncthreads();                                               // the children were written by this workgroup
+        const int l = l0 - s;
+        const unsigned mm = (base >> (2 * s)) + threadIdx.x;
+        if (threadIdx.x < (unsigned)(TSNE_TPB >> (2 * s)) && mm < (1u << (2 * l))) {
+            const double2 *ch = nsum + tree_level_offset(l + 1) + 4u * mm;
+            double sx = 0.0, sy = 0.0;
+            for (int c = 0; c < 4; ++c) { sx += ch[c].x; sy += ch[c].y; }
+            nsum[tree_level_offset(l) + mm] = make_double2(sx, sy);
+        }
+    }
+}
+
+// in place: {sum x, sum y} f64 -> {count, com.x, com.y, 0}; an empty node (or a range that runs backwards) gets count 0, com 0
+__global__ __launch_bounds__(TSNE_TPB) void k_tree_finalize(void *nodes, const int *__restrict__ start, int L, unsigned nn)
+{
+    const unsigned idx = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (idx >= nn) return;
+    int l = 0;
+    while (l < L && tree_level_offset(l + 1) <= idx) ++l;
+    const unsigned m = idx - tree_level_offset(l);
+    const int sh = 2 * (L - l);
+    const int cnt = start[(m + 1u) << sh] - start[m << sh];
+    const double2 s = ((const double2 *)nodes)[idx];
+    int4 r = make_int4(0, 0, 0, 0);
+    if (cnt > 0) {
+        r.x = cnt;
+        r.y = __float_as_int((float)__ddiv_rn(s.x, (double)cnt));
+        r.z = __float_as_int((float)__ddiv_rn(s.y, (double)cnt));
+    }
+    ((int4 *)nodes)[idx] = r;
+}
+
+// One wave per 64 consecutive targets of the sorted order.  (l, m) is wave-uniform and moves in depth-first order: down to
+// (l + 1, 4 m) while any lane wants to open, else on to the next sibling, climbing while m & 3 == 3.  acc is the level at
+// which the lane accepted an ancestor of the current node (64: none, -1: no target): the lane sits out until the walk is back
+// at that level or above.  The node index only grows, and the loop carries the pyramid's node count as its trip bound.
+template <bool VISITS>
+__global__ __launch_bounds__(TSNE_TPB) void k_tsne_tree_repulsion(const int4 *__restrict__ node, const int *__restrict__ start,
+                                                                  const float2 *__restrict__ ysort, const int64_t *__restrict__ order,
+                                                                  const TreeHead *__restrict__ head, double *__restrict__ part,
+                                                                  double *__restrict__ zpart, int32_t *__restrict__ visits, int N, int L,
+                                                                  float th2)
+{
+    __shared__ double s_red[TSNE_TPB / VCY_WAVE];
+    const int p = blockIdx.x * TSNE_TPB + threadIdx.x;
+    const bool valid = p < N;
+    const float2 tp = valid ? ysort[p] : make_float2(0.0f, 0.0f);
+    const float t[2] = {tp.x, tp.y};
+    int acc = valid ? 64 : -1;
+    double F[2] = {0.0, 0.0}, W = 0.0;
+    float f[2] = {0.0f, 0.0f}, w = 0.0f;
+    int run = 0, n_acc = 0, n_dir = 0;
+    const unsigned nn = tree_level_offset(L + 1);
+    int l = 0;
+    unsigned m = 0;
+    auto carry = [&]() {
+        F[0] += (double)f[0]; F[1] += (double)f[1]; W += (double)w;
+        f[0] = f[1] = w = 0.0f;
+        run = 0;
+    };
+    for (unsigned trip = 0; trip < nn; ++trip) {
+        const int4 nd = node[tree_level_offset(l) + m];
+        const int cnt = __builtin_amdgcn_readfirstlane(nd.x);
+        bool descend = false;
+        if (cnt > 0) {
+            if (acc >= l) acc = 64;
+            const bool active = acc == 64;
+            if (run + 1 > TREE_RUN) carry();
+            const float cx = __int_as_float(nd.y), cy = __int_as_float(nd.z);
+            const float dx = __fsub_rn(t[0], cx), dy = __fsub_rn(t[1], cy);
+            const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+            const bool take = active && head->w2[l] < __fmul_rn(th2, d2);
+            if (take) {                                                // the pair arithmetic of tsne_pair<2> with a multiplicity
+                const float q = __builtin_amdgcn_rcpf(fmaf(dy, dy, fmaf(dx, dx, 1.0f)));
+                const float cq = (float)cnt * q, cq2 = cq * q;
+                f[0] = fmaf(cq2, dx, f[0]);
+                f[1] = fmaf(cq2, dy, f[1]);
+                w += cq;
+                acc = l;
+                ++n_acc;
+            }
+            ++run;
+            const bool open = active && !take;
+            const bool any_open = __ballot(open) != 0ull;
+            if (l < L) {
+                descend = any_open;
+            } else if (any_open) {                                     // a leaf somebody does not accept: its points one by one
+                // 64 points per load, one per lane (every lane of the wave is here: the branch is uniform), then broadcast one by one
+                const int b = max(__builtin_amdgcn_readfirstlane(start[m]), 0), e = min(__builtin_amdgcn_readfirstlane(start[m + 1]), N);
+                for (int c0 = b; c0 < e; c0 += VCY_WAVE) {
+                    const int n = min(e - c0, VCY_WAVE), mine = c0 + (int)(threadIdx.x & 63);
+                    if (run + n > TREE_RUN) carry();
+                    const float2 sp = mine < e ? ysort[mine] : make_float2(0.0f, 0.0f);
+                    for (int u = 0; u < n; ++u) {
+                        const float s[2] = {readlane_t(sp.x, u), readlane_t(sp.y, u)};
+                        if (open && c0 + u != p) tsne_pair<2>(t, s, f, w);
+                    }
+                    run += n;
+                }
+                if (open && e > b) n_dir += (e - b) - (p >= b && p < e ? 1 : 0);
+            }
+        }
+        if (descend) {
+            ++l;
+            m <<= 2;
+        } else {
+            while (l > 0 && (m & 3u) == 3u) { m >>= 2; --l; }
+            if (l == 0) break;
+            ++m;
+        }
+    }
+    carry();
+    if (valid) {
+        const int64_t o64 = order[p];
+        const size_t o = (uint64_t)o64 < (uint64_t)N ? (size_t)o64 : 0;
+        part[o] = F[0];
+        part[(size_t)N + o] = F[1];
+        part[2 * (size_t)N + o] = W;
+        if constexpr (VISITS) { visits[2 * o] = n_acc; visits[2 * o + 1] = n_dir; }
+    }
+    const double zsum = block_sum(valid ? W : 0.0, s_red);
+    if (threadIdx.x == 0) zpart[blockIdx.x] = zsum;
+}
+
+// rep (N, 3) = force x, y and W of every point from part (3, N); Z = the sum of zpart in k_tsne_step's order
+__global__ __launch_bounds__(TSNE_TPB) void k_tree_rep_out(const double *__restrict__ part, const double *__restrict__ zpart, int nz,
+                                                           double *__restrict__ rep, double *__restrict__ Z, int N)
+{
+    __shared__ double s_red[TSNE_TPB / VCY_WAVE];
+    if (blockIdx.x == 0) {
+        const double z = tsne_fixed_sum(zpart, nz, s_red);
+        if (threadIdx.x == 0) Z[0] = z;
+    }
+    const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (i < N)
+        for (int a = 0; a < 3; ++a) rep[(size_t)i * 3 + a] = part[(size_t)a * N + i];
+}
+
+// build + traversal: part, zpart of the workspace are what k_tsne_step<2, .> reads with one split
+static int tree_repulsion_launch(const float *Y, const int64_t *order, const int32_t *skeys, int32_t *visits, void *workspace, const TreePlan &p,
+                                 int64_t N, double angle, hipStream_t s)
+{
+    char *w = (char *)workspace;
+    const int n = (int)N, L = p.L;
+    int *start = (int *)(w + p.start_off);
+    float2 *ysort = (float2 *)(w + p.ysort_off);
+    void *nodes = w + p.node_off;
+    hipLaunchKernelGGL(k_tree_start, dim3((unsigned)((p.cells + 1 + TSNE_TPB - 1) / TSNE_TPB)), dim3(TSNE_TPB), 0, s, skeys, start, n, (unsigned)p.cells);
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_tree_gather, dim3(p.nb), dim3(TSNE_TPB), 0, s, (const float2 *)Y, order, ysort, n);
+    VCY_LAUNCH_CHECK();
+    for (int l0 = L; l0 >= 0; l0 -= 5) {
+        const unsigned g = (unsigned)(((1ll << (2 * l0)) + TSNE_TPB - 1) / TSNE_TPB);
+        if (l0 == L)
+            hipLaunchKernelGGL(k_tree_up<true>, dim3(g), dim3(TSNE_TPB), 0, s, (double2 *)nodes, start, ysort, n, l0);
+        else
+            hipLaunchKernelGGL(k_tree_up<false>, dim3(g), dim3(TSNE_TPB), 0, s, (double2 *)nodes, start, ysort, n, l0);
+        VCY_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_tree_finalize, dim3((unsigned)((p.nodes + TSNE_TPB - 1) / TSNE_TPB)), dim3(TSNE_TPB), 0, s, nodes, start, L, (unsigned)p.nodes);
+    VCY_LAUNCH_CHECK();
+    const float th2 = (float)(angle * angle);
+    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off);
+    if (visits)
+        hipLaunchKernelGGL(k_tsne_tree_repulsion<true>, dim3(p.tb), dim3(TSNE_TPB), 0, s, (const int4 *)nodes, start, ysort, order,
+                           (const TreeHead *)w, part, zpart, visits, n, L, th2);
+    else
+        hipLaunchKernelGGL(k_tsne_tree_repulsion<false>, dim3(p.tb), dim3(TSNE_TPB), 0, s, (const int4 *)nodes, start, ysort, order,
+                           (const TreeHead *)w, part, zpart, visits, n, L, th2);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+static int tree_launch(const float *Y, float *Yout, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
+                       const int32_t *skeys, float *grad, double *update, float *gains, double *stats, void *workspace, int64_t N, int depth,
+                       double angle, int compute_error, double momentum, double lr, double min_gain, bool step, hipStream_t s)
+{
+    const TreePlan p = tree_plan(N, depth);
+    const int rc = tree_repulsion_launch(Y, order, skeys, nullptr, workspace, p, N, angle, s);
+    if (rc != VCY_OK) return rc;
+    char *w = (char *)workspace;
+    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off), *blk = (double *)(w + p.blk_off);
+    const int n = (int)N;
+    if (step)
+        hipLaunchKernelGGL((k_tsne_step<2, true>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
+                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
+    else
+        hipLaunchKernelGGL((k_tsne_step<2, false>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
+                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
+    VCY_LAUNCH_CHECK();
+    if (compute_error) {
+        hipLaunchKernelGGL(k_tsne_stats, dim3(1), dim3(TSNE_TPB), 0, s, blk, p.nb, stats);
+        VCY_LAUNCH_CHECK();
+    }
+    return VCY_OK;
+}
+
+static int tree_check(int64_t N, int n_components, int depth, double angle, const char *who)
+{
+    if (n_components != 2) return fail(VCY_ERR_UNSUPPORTED, "%s: the tree repulsion covers n_components == 2 only", who);
+    if (!(N >= 2 && N < (1ll << 30))) return fail(VCY_ERR_INVALID, "%s: N out of range", who);
+    if (depth < 1 || depth > TREE_MAX_DEPTH) return fail(VCY_ERR_INVALID, "%s: depth must be 1 .. 11", who);
+    if (!(angle >= 0.0 && angle <= 1.0)) return fail(VCY_ERR_INVALID, "%s: angle must be in [0, 1]", who);
+    return VCY_OK;
+}
+
 }  // namespace vcy
 
 using namespace vcy;
@@ -352,4 +734,72 @@ extern "C" int vcy_tsne_step(const float *Y, float *Y_out, const int64_t *indptr
     VCY_REQUIRE(n_components >= 1 && n_components <= 3, "tsne_step: n_components must be 1, 2 or 3");
     return tsne_dispatch(Y, Y_out, indptr, indices, pval, nullptr, update, gains, stats, workspace, N, n_components, compute_error, momentum,
                          learning_rate, min_gain, true, (hipStream_t)stream);
+}
+
+extern "C" int vcy_tsne_tree_depth(int64_t N)
+{
+    int L = 1;                                                         // at most 4 points per leaf on average (measured: DESIGN.md section 9)
+    while (L < TREE_MAX_DEPTH && (4ll << (2 * L)) < N) ++L;
+    return L;
+}
+
+extern "C" size_t vcy_tsne_tree_workspace_bytes(int64_t N, int depth)
+{
+    if (N < 2 || N >= (1ll << 30) || depth < 1 || depth > TREE_MAX_DEPTH) return 0;
+    return tree_plan(N, depth).bytes;
+}
+
+extern "C" int vcy_tsne_tree_keys(const float *Y, int32_t *keys, void *workspace, int64_t N, int depth, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && keys && workspace, "tsne_tree_keys: null pointer");
+    const int rc = tree_check(N, 2, depth, 0.0, "tsne_tree_keys");
+    if (rc != VCY_OK) return rc;
+    const TreePlan p = tree_plan(N, depth);
+    char *w = (char *)workspace;
+    float4 *boxp = (float4 *)(w + p.boxp_off);
+    hipLaunchKernelGGL(k_tree_box, dim3(p.nbx), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, (int)N);
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_tree_keys, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, p.nbx, (TreeHead *)w, keys, (int)N, depth);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_tsne_tree_repulsion(const float *Y, const int64_t *order, const int32_t *sorted_keys, double *rep, double *Z, int32_t *visits,
+                                       void *workspace, int64_t N, int depth, double angle, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && order && sorted_keys && rep && Z && workspace, "tsne_tree_repulsion: null pointer");
+    const int rc = tree_check(N, 2, depth, angle, "tsne_tree_repulsion");
+    if (rc != VCY_OK) return rc;
+    const TreePlan p = tree_plan(N, depth);
+    const int rc2 = tree_repulsion_launch(Y, order, sorted_keys, visits, workspace, p, N, angle, (hipStream_t)stream);
+    if (rc2 != VCY_OK) return rc2;
+    char *w = (char *)workspace;
+    hipLaunchKernelGGL(k_tree_rep_out, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const double *)(w + p.part_off),
+                       (const double *)(w + p.zpart_off), p.tb, rep, Z, (int)N);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_tsne_tree_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
+                                      const int32_t *sorted_keys, float *grad, double *stats, void *workspace, int64_t N, int n_components,
+                                      int depth, double angle, int compute_error, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && indptr && indices && pval && order && sorted_keys && grad && stats && workspace, "tsne_tree_gradient: null pointer");
+    const int rc = tree_check(N, n_components, depth, angle, "tsne_tree_gradient");
+    if (rc != VCY_OK) return rc;
+    return tree_launch(Y, nullptr, indptr, indices, pval, order, sorted_keys, grad, nullptr, nullptr, stats, workspace, N, depth, angle,
+                       compute_error, 0.0, 0.0, 0.0, false, (hipStream_t)stream);
+}
+
+extern "C" int vcy_tsne_tree_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval,
+                                  const int64_t *order, const int32_t *sorted_keys, double *update, float *gains, double *stats, void *workspace,
+                                  int64_t N, int n_components, int depth, double angle, double momentum, double learning_rate, double min_gain,
+                                  int compute_error, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && Y_out && indptr && indices && pval && order && sorted_keys && update && gains && stats && workspace, "tsne_tree_step: null pointer");
+    VCY_REQUIRE(Y != Y_out, "tsne_tree_step: Y_out must not alias Y (the attraction reads every row's old position)");
+    const int rc = tree_check(N, n_components, depth, angle, "tsne_tree_step");
+    if (rc != VCY_OK) return rc;
+    return tree_launch(Y, Y_out, indptr, indices, pval, order, sorted_keys, nullptr, update, gains, stats, workspace, N, depth, angle,
+                       compute_error, momentum, learning_rate, min_gain, true, (hipStream_t)stream);
 }

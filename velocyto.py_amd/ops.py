@@ -1742,6 +1742,91 @@ def tsne_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, indice
                                         float(min_gain), int(compute_error), _stream()), "tsne_step")
 
 
+def tsne_tree_depth(N: int) -> int:
+    """The automatic depth of the tree repulsion's quadtree for N points (vcy_tsne_tree_depth)."""
+    return int(_lib.lib().vcy_tsne_tree_depth(int(N)))
+
+
+def tsne_tree_workspace(N: int, depth: int) -> torch.Tensor:
+    nbytes = int(_lib.lib().vcy_tsne_tree_workspace_bytes(int(N), int(depth)))
+    if nbytes == 0:
+        raise ValueError(f"tsne_tree_workspace: N = {N} (>= 2) or depth = {depth} (1 .. 11) out of range")
+    return torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
+
+
+def _tsne_tree_args(Y: torch.Tensor, ws: torch.Tensor, depth: int, order: Optional[torch.Tensor] = None,
+                    sorted_keys: Optional[torch.Tensor] = None) -> int:
+    if Y.dim() != 2 or Y.dtype != torch.float32 or not Y.is_contiguous():
+        raise ValueError("t-SNE positions must be a contiguous (N, n_components) float32 device tensor")
+    N = Y.shape[0]
+    need = int(_lib.lib().vcy_tsne_tree_workspace_bytes(N, int(depth)))
+    if need == 0 or ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError("t-SNE tree: depth must be 1 .. 11, N >= 2 and the workspace that of tsne_tree_workspace(N, depth)")
+    if order is not None and not (order.dtype == torch.int64 and order.numel() == N and order.is_contiguous() and sorted_keys.dtype == torch.int32
+                                  and sorted_keys.numel() == N and sorted_keys.is_contiguous()):
+        raise ValueError("t-SNE tree: order must be (N) int64 and sorted_keys (N) int32 (tsne_tree_keys)")
+    return N
+
+
+def tsne_tree_keys(Y: torch.Tensor, ws: torch.Tensor, depth: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The first half of a tree-repulsion evaluation of positions Y (N, 2) f32: the bounding box goes into the workspace, every
+    point's leaf-cell Morton key is computed (vcy_tsne_tree_keys) and sorted (torch.sort, stable: plumbing, no host read).
+    Returns (keys (N) int32, order (N) int64, sorted keys (N) int32); order, the sorted keys and the same workspace go to
+    tsne_tree_repulsion / tsne_tree_gradient / tsne_tree_step."""
+    N = _tsne_tree_args(Y, ws, depth)
+    if Y.shape[1] != 2:
+        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
+    keys = torch.empty(N, dtype=torch.int32, device=Y.device)
+    _lib.check(_lib.lib().vcy_tsne_tree_keys(Y.data_ptr(), keys.data_ptr(), ws.data_ptr(), N, int(depth), _stream()), "tsne_tree_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    return keys, order, skeys
+
+
+def tsne_tree_repulsion(Y: torch.Tensor, order: torch.Tensor, sorted_keys: torch.Tensor, ws: torch.Tensor, depth: int, angle: float,
+                        visits: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """The Barnes-Hut repulsion alone: (rep (N, 3) f64 = force x, y and sum_j w_ij per point, Z (1) f64, visits (N, 2) int32 =
+    accepted nodes and directly summed points per target, or None)."""
+    N = _tsne_tree_args(Y, ws, depth, order, sorted_keys)
+    if Y.shape[1] != 2:
+        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
+    rep = torch.empty((N, 3), dtype=torch.float64, device=Y.device)
+    Z = torch.empty(1, dtype=torch.float64, device=Y.device)
+    vis = torch.empty((N, 2), dtype=torch.int32, device=Y.device) if visits else None
+    _lib.check(_lib.lib().vcy_tsne_tree_repulsion(Y.data_ptr(), order.data_ptr(), sorted_keys.data_ptr(), rep.data_ptr(), Z.data_ptr(),
+                                                  vis.data_ptr() if visits else None, ws.data_ptr(), N, int(depth), float(angle), _stream()),
+               "tsne_tree_repulsion")
+    return rep, Z, vis
+
+
+def tsne_tree_gradient(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
+                       sorted_keys: torch.Tensor, ws: torch.Tensor, depth: int, angle: float,
+                       compute_error: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """tsne_gradient with the tree repulsion at ``angle`` (0: the exact sum): (grad (N, 2) f32, stats (4) f64)."""
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    _tsne_tree_args(Y, ws, depth, order, sorted_keys)
+    grad = torch.empty_like(Y)
+    stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
+    _lib.check(_lib.lib().vcy_tsne_tree_gradient(Y.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), order.data_ptr(),
+                                                 sorted_keys.data_ptr(), grad.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, int(depth),
+                                                 float(angle), int(compute_error), _stream()), "tsne_tree_gradient")
+    return grad, stats
+
+
+def tsne_tree_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
+                   sorted_keys: torch.Tensor, update: torch.Tensor, gains: torch.Tensor, stats: torch.Tensor, ws: torch.Tensor, depth: int,
+                   angle: float, momentum: float, learning_rate: float, min_gain: float = 0.01, compute_error: bool = False) -> None:
+    """tsne_step with the tree repulsion at ``angle``; order and sorted_keys are tsne_tree_keys' of the same Y and workspace."""
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    _tsne_tree_args(Y, ws, depth, order, sorted_keys)
+    if not (Y_out.shape == Y.shape and Y_out.dtype == torch.float32 and update.shape == Y.shape and update.dtype == torch.float64
+            and gains.shape == Y.shape and gains.dtype == torch.float32 and stats.numel() >= 4 and stats.dtype == torch.float64):
+        raise ValueError("tsne_tree_step: Y_out (N, 2) f32, update (N, 2) f64, gains (N, 2) f32 and stats (4) f64")
+    _lib.check(_lib.lib().vcy_tsne_tree_step(Y.data_ptr(), Y_out.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(),
+                                             order.data_ptr(), sorted_keys.data_ptr(), update.data_ptr(), gains.data_ptr(), stats.data_ptr(),
+                                             ws.data_ptr(), N, d, int(depth), float(angle), float(momentum), float(learning_rate),
+                                             float(min_gain), int(compute_error), _stream()), "tsne_tree_step")
+
+
 def select_cells(M, keep) -> "CellMatrix":
     """Cell (row) subset of a cells-major matrix (CellMatrix or CountMatrix)."""
     idx = torch.nonzero(torch.as_tensor(keep, device=M.t.device), as_tuple=False).ravel()

@@ -10,8 +10,10 @@ The same as scikit-learn 1.7 (manifold/_t_sne.py, _utils.pyx, _barnes_hut_tsne.p
     checks every 50 iterations; positions, gains and gradient in f32, the update in f64 as numpy 2 makes it; the ``"random"``
     start is bit-equal to scikit-learn's for the same ``random_state``.
 Different:
-  * the repulsion is summed EXACTLY over all pairs, so ``angle`` is accepted and ignored: the result is the angle -> 0 limit of
-    scikit-learn's Barnes-Hut gradient, at O(N^2) work per iteration (DESIGN.md section 9);
+  * by default (``repulsion="exact"``) the repulsion is summed EXACTLY over all pairs, so ``angle`` is accepted and ignored: the
+    result is the angle -> 0 limit of scikit-learn's Barnes-Hut gradient, at O(N^2) work per iteration (DESIGN.md section 9);
+    ``repulsion="tree"`` (n_components == 2) applies scikit-learn's acceptance rule with ``angle`` on a complete quadtree of fixed
+    depth rebuilt every iteration (scikit-learn's tree is adaptive, so the two accept different nodes at the same angle);
   * only the point itself is left out of its own repulsion; scikit-learn's tree also drops points that coincide with it within
     its EPSILON (neighbors/_quad_tree.pyx:413-421), so exact duplicates repel each other here;
   * KL, Z and |grad| are summed in f64 (scikit-learn sums the error in f32);
@@ -71,14 +73,20 @@ def _symmetrize(idx: torch.Tensor, cond: torch.Tensor) -> Tuple[torch.Tensor, to
 class DeviceTSNE:
     """``sklearn.manifold.TSNE(method="barnes_hut", metric="euclidean")`` on the device: the same constructor arguments,
     ``fit_transform`` and the fitted attributes ``embedding_``, ``kl_divergence_``, ``n_iter_``, ``learning_rate_``,
-    ``n_features_in_``.  ``angle`` is accepted and IGNORED: the repulsion is exact (see the module docstring for what else differs)."""
+    ``n_features_in_`` (see the module docstring for what differs).
+
+    repulsion: ``"exact"`` (the default) sums the repulsion over all pairs, O(N^2) per iteration; ``angle`` is accepted and IGNORED.
+    ``"tree"`` (n_components == 2 only) uses scikit-learn's Barnes-Hut acceptance rule with ``angle`` (0 <= angle <= 1) on a quadtree
+    of ``tree_depth`` levels (None: ``ops.tsne_tree_depth(N)``), O(N log N); its iteration is the faster one above about 50 000
+    points (DESIGN.md section 9 has the measurements)."""
 
     _EXPLORATION_MAX_ITER = 250
     _N_ITER_CHECK = 50
 
     def __init__(self, n_components: int = 2, *, perplexity: float = 30.0, early_exaggeration: float = 12.0, learning_rate="auto",
                  max_iter: int = 1000, n_iter_without_progress: int = 300, min_grad_norm: float = 1e-7, init="random", random_state=None,
-                 angle: float = 0.5):
+                 angle: float = 0.5, repulsion: str = "exact", tree_depth=None):
+        self.repulsion, self.tree_depth = repulsion, tree_depth
         self.n_components, self.perplexity, self.early_exaggeration = n_components, perplexity, early_exaggeration
         self.learning_rate, self.max_iter, self.n_iter_without_progress = learning_rate, max_iter, n_iter_without_progress
         self.min_grad_norm, self.init, self.random_state, self.angle = min_grad_norm, init, random_state, angle
@@ -89,6 +97,7 @@ class DeviceTSNE:
             raise ValueError(f"Expected 2D array, got array with shape {tuple(shape)}")
         N = shape[0]
         nc = self.n_components
+        self._check_repulsion(self.repulsion, nc, self.angle, self.tree_depth)
         if not isinstance(nc, numbers.Integral) or isinstance(nc, bool) or nc < 1:
             raise ValueError(f"The 'n_components' parameter of TSNE must be an int in the range [1, inf). Got {nc!r} instead.")
         if not (isinstance(self.perplexity, numbers.Real) and self.perplexity > 0):
@@ -113,6 +122,18 @@ class DeviceTSNE:
             raise ValueError(f"Found array with {N} sample(s) (shape={tuple(shape)}) while a minimum of 2 is required by TSNE.")
         if nc > 3:
             raise ValueError("'n_components' should be inferior to 4 for the barnes_hut algorithm as it relies on quad-tree or oct-tree.")
+
+    @staticmethod
+    def _check_repulsion(repulsion, n_components, angle, tree_depth) -> None:
+        if repulsion not in ("exact", "tree"):
+            raise ValueError(f"The 'repulsion' parameter of DeviceTSNE must be 'exact' or 'tree'. Got {repulsion!r} instead.")
+        if repulsion == "tree":
+            if n_components != 2:
+                raise NotImplementedError("DeviceTSNE: repulsion='tree' is implemented for n_components == 2 only")
+            if not (isinstance(angle, numbers.Real) and 0.0 <= angle <= 1.0):
+                raise ValueError(f"The 'angle' parameter of TSNE must be a float in the range [0.0, 1.0]. Got {angle!r} instead.")
+            if tree_depth is not None and not (isinstance(tree_depth, numbers.Integral) and 1 <= tree_depth <= 11):
+                raise ValueError(f"tree_depth must be None or an int in the range [1, 11]. Got {tree_depth!r} instead.")
 
     def fit_transform(self, X, y=None) -> np.ndarray:
         """X: (n_samples, n_features) host array or device tensor.  Returns the embedding (n_samples, n_components) float32."""
@@ -167,23 +188,40 @@ class DeviceTSNE:
     def _gradient_descent(self, Y: torch.Tensor, csr, it: int, max_iter: int, momentum: float, n_iter_without_progress: int):
         """_gradient_descent (_t_sne.py:301-444) from positions Y (N, d) f32 on the device: fresh update and gains, one vcy_tsne_step
         per iteration on one stream; the host reads back [Z, KL, |grad|^2] only where scikit-learn computes the error (every 50th
-        iteration and the last).  Returns (positions, error, last iteration)."""
+        iteration and the last).  Returns (positions, error, last iteration).
+        repulsion="tree": per iteration the keys, their sort and vcy_tsne_tree_step; the read at a check also carries whether the
+        new positions are finite, and a fit whose positions are not stops there with a FloatingPointError."""
         indptr, indices, pval = csr
         N, d = Y.shape
+        tree = self.repulsion == "tree"
+        if tree:
+            self._check_repulsion(self.repulsion, d, self.angle, self.tree_depth)
+            depth = ops.tsne_tree_depth(N) if self.tree_depth is None else int(self.tree_depth)
+            tws = ops.tsne_tree_workspace(N, depth)
         update = torch.zeros((N, d), dtype=torch.float64, device=Y.device)
         gains = torch.ones((N, d), dtype=torch.float32, device=Y.device)
         Y_next = torch.empty_like(Y)
         stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
-        ws = ops.tsne_workspace(N, d)
+        ws = None if tree else ops.tsne_workspace(N, d)
         lr = float(self.learning_rate_)
         error = best_error = np.finfo(float).max
         best_iter = i = it
         for i in range(it, max_iter):
             check = (i + 1) % self._N_ITER_CHECK == 0
             want = check or i == max_iter - 1
-            ops.tsne_step(Y, Y_next, indptr, indices, pval, update, gains, stats, ws, momentum, lr, 0.01, want)
+            if tree:
+                _, order, skeys = ops.tsne_tree_keys(Y, tws, depth)
+                ops.tsne_tree_step(Y, Y_next, indptr, indices, pval, order, skeys, update, gains, stats, tws, depth, self.angle, momentum, lr,
+                                   0.01, want)
+            else:
+                ops.tsne_step(Y, Y_next, indptr, indices, pval, update, gains, stats, ws, momentum, lr, 0.01, want)
             Y, Y_next = Y_next, Y
-            if want:
+            if want and tree:
+                h = torch.cat([stats, torch.isfinite(Y).all().to(torch.float64).reshape(1)]).cpu().numpy()
+                if h[4] != 1.0 or not np.all(np.isfinite(h[:3])):
+                    raise FloatingPointError(f"DeviceTSNE(repulsion='tree'): non-finite positions or objective at iteration {i}")
+                error = float(h[1])
+            elif want:
                 h = stats.cpu().numpy()
                 error = float(h[1])
             if check:
@@ -205,9 +243,17 @@ class DeviceTSNE:
                torch.from_numpy(np.asarray(P.data, dtype=np.float32)).to(dev))
         return Yd, csr
 
-    def _objective(self, Y, P) -> Tuple[float, np.ndarray]:
-        """(KL, grad (N, d) f32) of _kl_divergence_bh at angle = 0 for positions Y and a scipy CSR P (its values read as f32)."""
+    def _objective(self, Y, P, repulsion: str = "exact", angle: float = 0.5, tree_depth=None) -> Tuple[float, np.ndarray]:
+        """(KL, grad (N, d) f32) for positions Y and a scipy CSR P (its values read as f32): of _kl_divergence_bh at angle = 0
+        (repulsion="exact"), or with the tree repulsion at ``angle`` (repulsion="tree")."""
         Yd, csr = self._device_args(Y, P)
+        self._check_repulsion(repulsion, Yd.shape[1], angle, tree_depth)
+        if repulsion == "tree":
+            depth = ops.tsne_tree_depth(Yd.shape[0]) if tree_depth is None else int(tree_depth)
+            tws = ops.tsne_tree_workspace(Yd.shape[0], depth)
+            _, order, skeys = ops.tsne_tree_keys(Yd, tws, depth)
+            grad, stats = ops.tsne_tree_gradient(Yd, *csr, order, skeys, tws, depth, angle, compute_error=True)
+            return float(stats[1]), grad.cpu().numpy()
         grad, stats = ops.tsne_gradient(Yd, *csr, compute_error=True)
         return float(stats[1]), grad.cpu().numpy()
 
