@@ -687,6 +687,37 @@ int vcy_tsne_tree_step(const float *Y, float *Y_out, const int64_t *indptr, cons
                        int64_t N, int n_components, int depth, double angle, double momentum, double learning_rate, double min_gain,
                        int compute_error, vcy_stream stream);
 
+/* The same repulsion on a quadtree whose depth follows the density (opt-in; the entry points above are unchanged): the box, the
+ * acceptance rule and the pair arithmetic are the fixed tree's.  Keys are int64: the Morton interleave (x in the even bits) of two
+ * max_depth-bit cell numbers, 1 <= max_depth <= 24.  The root (level 0) holds all points; a node of level l with n points is a leaf
+ * iff n <= leaf_size (>= 1) or l == max_depth, otherwise its children are the non-empty ones of its four level-(l + 1) cells in Morton
+ * order.  Nodes are numbered in depth-first preorder.  A leaf's f64 sum runs over its points in sorted order from 0.0, an internal
+ * node's is 0.0 + its children's sums in child order, com = f32(sum / count); no atomics.  Per evaluation: vcy_tsne_atree_keys (box
+ * and head into the workspace, keys (N) int64), the caller's stable sort (order (N) int64, sorted_keys (N) int64), then with the SAME
+ * workspace vcy_tsne_atree_repulsion / _gradient / _step, whose other arguments are those of their vcy_tsne_tree_* namesakes.
+ * Workspace, vcy_tsne_atree_workspace_bytes(N, leaf_size, max_depth) bytes (0: arguments out of range, which includes a node bound
+ * cap = 1 + 4 max_depth floor(N / (leaf_size + 1)) of 2^31 or more), in 128-byte aligned sections:
+ *   head, 256 bytes: lo x, lo y, side, 2^max_depth / side f64; 25 f32 = f32((side 2^-l)^2); int32 node count of the evaluation
+ *     (byte 132); int32 max_depth, leaf_size; zero padding
+ *   | 256 x 16 bytes of box partials
+ *   | node records, cap x 32 bytes {int32 start, count (the range [start, start + count) of the sorted order), level, skip (the
+ *     number of the first node after the subtree); f32 com x, com y; int32 leaf (1 / 0), 0}
+ *   | node sums, cap x 16 bytes {f64 sum x, sum y}
+ *   | int32 (N): nodes starting at a sorted position | their first level << 8 | last level << 16
+ *   | int32 (N + 1) and int32 (ceil(N / 2048) + 1): the scan of those counts inside chunks of 2048 positions and over the chunks
+ *   | sorted positions (N, 2) f32 | part (3, N) f64 | per-workgroup partials. */
+size_t vcy_tsne_atree_workspace_bytes(int64_t N, int leaf_size, int max_depth);
+int vcy_tsne_atree_keys(const float *Y, int64_t *keys, void *workspace, int64_t N, int leaf_size, int max_depth, vcy_stream stream);
+int vcy_tsne_atree_repulsion(const float *Y, const int64_t *order, const int64_t *sorted_keys, double *rep, double *Z, int32_t *visits,
+                             void *workspace, int64_t N, int leaf_size, int max_depth, double angle, vcy_stream stream);
+int vcy_tsne_atree_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
+                            const int64_t *sorted_keys, float *grad, double *stats, void *workspace, int64_t N, int n_components,
+                            int leaf_size, int max_depth, double angle, int compute_error, vcy_stream stream);
+int vcy_tsne_atree_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval,
+                        const int64_t *order, const int64_t *sorted_keys, double *update, float *gains, double *stats, void *workspace,
+                        int64_t N, int n_components, int leaf_size, int max_depth, double angle, double momentum, double learning_rate,
+                        double min_gain, int compute_error, vcy_stream stream);
+
 /* ---------------------------------------------------------------- upstream caller: PCA straight from CSR count layers
  * perform_PCA on S_norm = log2(S_sz + pcount) (analysis.py:549-551, 678-700) where the layer only exists as CSR counts (the atlas
  * path; the reference forms S_norm dense in float64).  A stored count c stands for x = log2(c * s + pcount) - log2(pcount), computed

@@ -101,6 +101,12 @@ SIGNATURES = {
     "vcy_tsne_tree_gradient": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_dbl, c_int, c_vp]),
     "vcy_tsne_tree_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_dbl,
                                    c_dbl, c_dbl, c_dbl, c_int, c_vp]),
+    "vcy_tsne_atree_workspace_bytes": (c_sz, [c_i64, c_int, c_int]),
+    "vcy_tsne_atree_keys": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "vcy_tsne_atree_repulsion": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_dbl, c_vp]),
+    "vcy_tsne_atree_gradient": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_int, c_vp]),
+    "vcy_tsne_atree_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_dbl,
+                                    c_dbl, c_dbl, c_dbl, c_int, c_vp]),
     "vcy_csr_spmm_chunk": (c_i64, []),
     "vcy_csr_spmm_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_csr_lognorm_spmm": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_dbl, c_int, c_int, c_vp]),

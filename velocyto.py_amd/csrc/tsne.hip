@@ -693,6 +693,430 @@ static int tree_check(int64_t N, int n_components, int depth, double angle, cons
     return VCY_OK;
 }
 
+// ---------------------------------------------------------------- adaptive tree repulsion (D = 2, opt-in)
+// The same box, acceptance rule and pair arithmetic on a quadtree whose depth follows the density (vcy_tsne_atree_*; DESIGN.md
+// section 9): int64 Morton keys of `depth` (1 .. 24) bits per axis; a node of level l with n points is a leaf iff n <= leaf_size or
+// l == depth, otherwise its children are its non-empty level-(l + 1) cells; nodes in depth-first preorder, each with `skip` = the
+// first node after its subtree.  Built from the sorted keys without a launch per level:
+//   k_atree_keys    the box, the head and every point's key
+//   [the caller sorts the keys]
+//   k_atree_flag    position i starts the nodes of levels l0(i) .. l1(i): l0 = first level at which the key prefix differs from
+//                   position i - 1, l1 = min(depth, 1 + deepest level whose cell around i holds > leaf_size points) (a binary search
+//                   over levels, each probe two binary searches in the keys); also the positions in sorted order
+//   k_atree_scan1 / k_atree_scan2   exclusive scan of the per-position node counts: preorder = order by (start position, level)
+//   k_atree_emit    node records {start, count, level, skip, com, leaf}; skip = the number of the first node starting at the node's end
+//   k_atree_com     per level, deepest first: f64 sums (a leaf's points in sorted order, an internal node's children in child order)
+//                   and com = f32(sum / count): no atomics
+//   k_tsne_atree_repulsion   one wave per 64 consecutive sorted targets, the node number wave-uniform
+// Workspace: ATreeHead (256 bytes) | box partials | node records 32 bytes x cap | node sums 16 bytes x cap | per-position node
+// count and levels | scan | chunk offsets | sorted positions | part (3, N) f64 | zpart | blk.  cap = 1 + 4 depth floor(N / (leaf_size + 1)).
+constexpr int ATREE_MAX_DEPTH = 24;
+constexpr int ATREE_SCAN_ITEMS = 8;                                    // positions per thread of the scan
+constexpr int ATREE_SCAN_CHUNK = TSNE_TPB * ATREE_SCAN_ITEMS;
+constexpr int ATREE_GRID = 2048;                                       // workgroups of the kernels that loop over the nodes (their number is on the device)
+
+struct ATreeHead {
+    double lo[2], side, scale;                     // box corner, larger extent, 2^depth / side (0 when side is 0 or not finite)
+    float w2[ATREE_MAX_DEPTH + 1];                 // f32((side 2^-l)^2)
+    int n_nodes;                                   // nodes of this evaluation (<= cap)
+    int depth, leaf_size;
+    int pad[28];
+};
+static_assert(sizeof(ATreeHead) == 256, "ATreeHead");
+
+struct ATreeNode {                                 // 32 bytes: one scalar load
+    int start, count, level, skip;                 // range [start, start + count) of the sorted order
+    float cx, cy;                                  // centre of mass
+    int leaf, pad;
+};
+static_assert(sizeof(ATreeNode) == 32, "ATreeNode");
+
+struct ATreePlan {
+    int D, leaf, nbx, tb, nb, nchunk;
+    int64_t cap;
+    size_t boxp_off, node_off, nsum_off, flag_off, scan_off, chunk_off, ysort_off, part_off, zpart_off, blk_off, bytes;
+};
+static int64_t atree_cap(int64_t N, int leaf, int D) { return 1 + 4 * (int64_t)D * (N / ((int64_t)leaf + 1)); }
+static ATreePlan atree_plan(int64_t N, int leaf, int D)
+{
+    ATreePlan p;
+    p.D = D;
+    p.leaf = leaf;
+    p.cap = atree_cap(N, leaf, D);
+    p.nbx = (int)((N + TSNE_TPB - 1) / TSNE_TPB < TREE_BOX_BLOCKS ? (N + TSNE_TPB - 1) / TSNE_TPB : TREE_BOX_BLOCKS);
+    p.tb = p.nb = (int)((N + TSNE_TPB - 1) / TSNE_TPB);
+    p.nchunk = (int)((N + ATREE_SCAN_CHUNK - 1) / ATREE_SCAN_CHUNK);
+    p.boxp_off = sizeof(ATreeHead);
+    p.node_off = p.boxp_off + tree_align(sizeof(float4) * TREE_BOX_BLOCKS);
+    p.nsum_off = p.node_off + tree_align(sizeof(ATreeNode) * (size_t)p.cap);
+    p.flag_off = p.nsum_off + tree_align(sizeof(double2) * (size_t)p.cap);
+    p.scan_off = p.flag_off + tree_align(sizeof(int) * (size_t)N);
+    p.chunk_off = p.scan_off + tree_align(sizeof(int) * (size_t)(N + 1));
+    p.ysort_off = p.chunk_off + tree_align(sizeof(int) * (size_t)(p.nchunk + 1));
+    p.part_off = p.ysort_off + tree_align(sizeof(float2) * (size_t)N);
+    p.zpart_off = p.part_off + tree_align(sizeof(double) * 3 * (size_t)N);
+    p.blk_off = p.zpart_off + tree_align(sizeof(double) * (size_t)p.tb);
+    p.bytes = p.blk_off + tree_align(sizeof(double) * 2 * (size_t)p.nb);
+    return p;
+}
+
+__device__ __forceinline__ unsigned long long atree_spread(unsigned x)
+{
+    unsigned long long v = x & 0xffffffu;
+    v = (v | (v << 16)) & 0x0000ffff0000ffffull;
+    v = (v | (v << 8)) & 0x00ff00ff00ff00ffull;
+    v = (v | (v << 4)) & 0x0f0f0f0f0f0f0f0full;
+    v = (v | (v << 2)) & 0x3333333333333333ull;
+    return (v | (v << 1)) & 0x5555555555555555ull;
+}
+
+__global__ __launch_bounds__(TSNE_TPB) void k_atree_keys(const float2 *__restrict__ Y, const float4 *__restrict__ boxp, int nbx,
+                                                         ATreeHead *__restrict__ head, int64_t *__restrict__ keys, int N, int D, int leaf)
+{
+    __shared__ float4 s_box[TSNE_TPB / VCY_WAVE];
+    float4 b = (int)threadIdx.x < nbx ? boxp[threadIdx.x] : make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
+    b = tree_block_box(b, s_box);                                      // every workgroup: the same box
+    const double lox = (double)b.x, loy = (double)b.y;
+    const double side = fmax(__dsub_rn((double)b.z, lox), __dsub_rn((double)b.w, loy));
+    const double scale = (side > 0.0 && side < INFINITY) ? __ddiv_rn((double)(1 << D), side) : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        head->lo[0] = lox; head->lo[1] = loy; head->side = side; head->scale = scale;
+        for (int l = 0; l <= ATREE_MAX_DEPTH; ++l) {
+            const double s = __dmul_rn(side, 1.0 / (double)(1 << l));
+            head->w2[l] = (float)__dmul_rn(s, s);
+        }
+        head->n_nodes = 0; head->depth = D; head->leaf_size = leaf;
+        for (int l = 0; l < 28; ++l) head->pad[l] = 0;
+    }
+    const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (i < N) {
+        const float2 y = Y[i];
+        keys[i] = (int64_t)(atree_spread(tree_cell(y.x, lox, scale, D)) | (atree_spread(tree_cell(y.y, loy, scale, D)) << 1));
+    }
+}
+
+// first position in [lo, hi) whose key is >= k (hi when there is none): in [lo, hi] whatever the keys hold
+__device__ __forceinline__ int atree_lower(const int64_t *__restrict__ sk, int lo, int hi, int64_t k)
+{
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (sk[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// flag[i] = nodes starting at position i | l0 << 8 | l1 << 16 (0: none); ysort = positions in sorted order
+__global__ __launch_bounds__(TSNE_TPB) void k_atree_flag(const int64_t *__restrict__ sk, const float2 *__restrict__ Y,
+                                                         const int64_t *__restrict__ order, int *__restrict__ flag, float2 *__restrict__ ysort,
+                                                         int N, int D, int leaf)
+{
+    const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (i >= N) return;
+    const int64_t o = order[i];
+    ysort[i] = Y[(uint64_t)o < (uint64_t)N ? o : 0];
+    const int64_t k = sk[i];
+    int l0 = 0;
+    if (i > 0) {
+        const unsigned long long x = (unsigned long long)(k ^ sk[i - 1]);
+        if (x == 0ull) { flag[i] = 0; return; }                        // a repeated key starts no node
+        l0 = D - ((63 - __clzll((long long)x)) >> 1);
+    }
+    // the deepest level in 0 .. D whose cell around i holds more than `leaf` points (-1: not even the root)
+    int a = -1, b = D;
+    while (a < b) {
+        const int l = a + ((b - a + 1) >> 1), sh = 2 * (D - l);
+        const int64_t c0 = (k >> sh) << sh;
+        const int first = atree_lower(sk, 0, i, c0), last = atree_lower(sk, i + 1, N, c0 + ((int64_t)1 << sh));
+        if (last - first > leaf) a = l; else b = l - 1;
+    }
+    const int l1 = min(D, a + 1);
+    l0 = min(max(l0, 0), D + 1);                                       // keys beyond 2 D bits (not this library's) start no node
+    const int n = max(l1 - l0 + 1, 0);
+    flag[i] = n ? (n | (l0 << 8) | (l1 << 16)) : 0;
+}
+
+// scan[i] = the node counts of the chunk's positions before i; chunk[c] = the chunk's total
+__global__ __launch_bounds__(TSNE_TPB) void k_atree_scan1(const int *__restrict__ flag, int *__restrict__ scan, int *__restrict__ chunk, int N)
+{
+    __shared__ int s_w[TSNE_TPB / VCY_WAVE];
+    const int base = blockIdx.x * ATREE_SCAN_CHUNK + threadIdx.x * ATREE_SCAN_ITEMS;
+    int v[ATREE_SCAN_ITEMS], tot = 0;
+#pragma unroll
+    for (int r = 0; r < ATREE_SCAN_ITEMS; ++r) {
+        v[r] = base + r < N ? (flag[base + r] & 0xff) : 0;
+        tot += v[r];
+    }
+    int inc = tot;                                                     // inclusive scan over the wave, then over the 4 waves
+#pragma unroll
+    for (int off = 1; off < VCY_WAVE; off <<= 1) {
+        const int o = __shfl_up(inc, off, VCY_WAVE);
+        if ((int)(threadIdx.x & 63) >= off) inc += o;
+    }
+    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    int before = inc - tot;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) before += s_w[w];
+#pragma unroll
+    for (int r = 0; r < ATREE_SCAN_ITEMS; ++r) {
+        if (base + r < N) scan[base + r] = before;
+        before += v[r];
+    }
+    if (threadIdx.x == TSNE_TPB - 1) chunk[blockIdx.x] = before;
+}
+
+// one workgroup: chunk[c] <- the totals of the chunks before c, chunk[nchunk] and head->n_nodes <- the number of nodes (<= cap)
+__global__ __launch_bounds__(TSNE_TPB) void k_atree_scan2(int *__restrict__ chunk, int nchunk, ATreeHead *__restrict__ head, int *__restrict__ scan,
+                                                          int N, long long cap)
+{
+    __shared__ int s_w[TSNE_TPB / VCY_WAVE];
+    long long carry = 0;
+    for (int c0 = 0; c0 < nchunk; c0 += TSNE_TPB) {
+        const int c = c0 + threadIdx.x;
+        const int v = c < nchunk ? chunk[c] : 0;
+        int inc = v;
+#pragma unroll
+        for (int off = 1; off < VCY_WAVE; off <<= 1) {
+            const int o = __shfl_up(inc, off, VCY_WAVE);
+            if ((int)(threadIdx.x & 63) >= off) inc += o;
+        }
+        __syncthreads();
+        if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = inc;
+        __syncthreads();
+        long long before = carry + inc - v;
+        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) before += s_w[w];
+        if (c < nchunk) chunk[c] = (int)(before < cap ? before : cap);
+        carry += (long long)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    }
+    if (threadIdx.x == 0) {
+        const int nn = (int)(carry < cap ? carry : cap);
+        chunk[nchunk] = nn;
+        scan[N] = 0;
+        head->n_nodes = nn;
+    }
+}
+
+__device__ __forceinline__ int atree_number(const int *__restrict__ scan, const int *__restrict__ chunk, int pos)
+{
+    return scan[pos] + chunk[pos / ATREE_SCAN_CHUNK];                  // pos == N: scan[N] = 0, chunk[nchunk] = the total when N fills its chunks,
+}                                                                      // and otherwise the callers pass `nn` for it
+
+// the records of the nodes that start at position i, levels l0 .. l1: the ends are nested, each searched inside the one before
+__global__ __launch_bounds__(TSNE_TPB) void k_atree_emit(const int64_t *__restrict__ sk, const int *__restrict__ flag, const int *__restrict__ scan,
+                                                         const int *__restrict__ chunk, int nchunk, ATreeNode *__restrict__ node, int N, int D,
+                                                         int leaf, long long cap)
+{
+    const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
+    if (i >= N) return;
+    const int fl = flag[i], n = fl & 0xff;
+    if (!n) return;
+    const int l0 = (fl >> 8) & 0xff, nn = chunk[nchunk];
+    const int64_t k = sk[i];
+    const int first = atree_number(scan, chunk, i);
+    int end = N;
+    for (int r = 0; r < n; ++r) {
+        const int l = l0 + r, sh = 2 * (D - l);
+        end = atree_lower(sk, i + 1, end, ((k >> sh) << sh) + ((int64_t)1 << sh));
+        const long long idx = (long long)first + r;
+        if (idx >= cap || idx >= nn) return;
+        ATreeNode nd;
+        nd.start = i;
+        nd.count = end - i;
+        nd.level = l;
+        nd.skip = end >= N ? nn : min(max(atree_number(scan, chunk, end), (int)idx + 1), nn);
+        nd.cx = nd.cy = 0.0f;
+        nd.leaf = (nd.count <= leaf || l >= D) ? 1 : 0;
+        nd.pad = 0;
+        node[idx] = nd;
+    }
+}
+
+// the nodes of level l (launched for l = depth .. 0): sum and com; the children are the next node and then each one's skip
+__global__ __launch_bounds__(TSNE_TPB) void k_atree_com(ATreeNode *node, double2 *nsum, const float2 *__restrict__ ysort,
+                                                        const ATreeHead *__restrict__ head, int N, int l)
+{
+    const int nn = head->n_nodes;
+    for (int idx = blockIdx.x * TSNE_TPB + threadIdx.x; idx < nn; idx += gridDim.x * TSNE_TPB) {
+        const ATreeNode nd = node[idx];
+        if (nd.level != l) continue;
+        double sx = 0.0, sy = 0.0;
+        if (nd.leaf) {
+            const int b = max(nd.start, 0), e = min(nd.start + nd.count, N);
+#pragma unroll 4
+            for (int j = b; j < e; ++j) {
+                const float2 y = ysort[j];
+                sx += (double)y.x;
+                sy += (double)y.y;
+            }
+        } else {
+            const int stop = min(nd.skip, nn);
+            int c = idx + 1;
+            for (int t = 0; t < 4 && c < stop; ++t) {
+                const double2 s = nsum[c];
+                sx += s.x;
+                sy += s.y;
+                c = max(node[c].skip, c + 1);
+            }
+        }
+        nsum[idx] = make_double2(sx, sy);
+        node[idx].cx = (float)__ddiv_rn(sx, (double)nd.count);
+        node[idx].cy = (float)__ddiv_rn(sy, (double)nd.count);
+    }
+}
+
+// One wave per 64 consecutive targets of the sorted order; the node number i is wave-uniform and only grows.  `until` is the
+// skip of the node the lane accepted last: the lane sits out while i < until (a lane without a target: always).  A node that no
+// lane wants to open is left for its skip, an internal node that some lane opens for i + 1, a leaf that some lane does not accept
+// is summed point by point by those lanes.  The loop carries the node count as its trip bound.
+template <bool VISITS>
+__global__ __launch_bounds__(TSNE_TPB) void k_tsne_atree_repulsion(const ATreeNode *__restrict__ node, const float2 *__restrict__ ysort,
+                                                                   const int64_t *__restrict__ order, const ATreeHead *__restrict__ head,
+                                                                   double *__restrict__ part, double *__restrict__ zpart,
+                                                                   int32_t *__restrict__ visits, int N, float th2)
+{
+    __shared__ double s_red[TSNE_TPB / VCY_WAVE];
+    const int p = blockIdx.x * TSNE_TPB + threadIdx.x;
+    const bool valid = p < N;
+    const float2 tp = valid ? ysort[p] : make_float2(0.0f, 0.0f);
+    const float t[2] = {tp.x, tp.y};
+    int until = valid ? 0 : 0x7fffffff;
+    double F[2] = {0.0, 0.0}, W = 0.0;
+    float f[2] = {0.0f, 0.0f}, w = 0.0f;
+    int run = 0, n_acc = 0, n_dir = 0;
+    const int nn = __builtin_amdgcn_readfirstlane(head->n_nodes);
+    auto carry = [&]() {
+        F[0] += (double)f[0]; F[1] += (double)f[1]; W += (double)w;
+        f[0] = f[1] = w = 0.0f;
+        run = 0;
+    };
+    int i = 0;
+    for (int trip = 0; trip < nn && i < nn; ++trip) {
+        i = __builtin_amdgcn_readfirstlane(i);
+        const ATreeNode nd = node[i];
+        const int cnt = __builtin_amdgcn_readfirstlane(nd.count), lvl = min(max(__builtin_amdgcn_readfirstlane(nd.level), 0), ATREE_MAX_DEPTH);
+        const int skip = max(__builtin_amdgcn_readfirstlane(nd.skip), i + 1), leaf = __builtin_amdgcn_readfirstlane(nd.leaf);
+        const bool active = i >= until;
+        if (run + 1 > TREE_RUN) carry();
+        const float dx = __fsub_rn(t[0], nd.cx), dy = __fsub_rn(t[1], nd.cy);
+        const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+        const bool take = active && head->w2[lvl] < __fmul_rn(th2, d2);
+        if (take) {                                                    // the pair arithmetic of tsne_pair<2> with a multiplicity
+            const float q = __builtin_amdgcn_rcpf(fmaf(dy, dy, fmaf(dx, dx, 1.0f)));
+            const float cq = (float)cnt * q, cq2 = cq * q;
+            f[0] = fmaf(cq2, dx, f[0]);
+            f[1] = fmaf(cq2, dy, f[1]);
+            w += cq;
+            until = skip;
+            ++n_acc;
+        }
+        ++run;
+        const bool open = active && !take;
+        const bool any_open = __ballot(open) != 0ull;
+        if (leaf && any_open) {
+            // 64 points per load, one per lane (every lane of the wave is here: the branch is uniform), then broadcast one by one
+            const int b = max(__builtin_amdgcn_readfirstlane(nd.start), 0), e = min(b + max(cnt, 0), N);
+            for (int c0 = b; c0 < e; c0 += VCY_WAVE) {
+                const int n = min(e - c0, VCY_WAVE), mine = c0 + (int)(threadIdx.x & 63);
+                if (run + n > TREE_RUN) carry();
+                const float2 sp = mine < e ? ysort[mine] : make_float2(0.0f, 0.0f);
+                for (int u = 0; u < n; ++u) {
+                    const float s[2] = {readlane_t(sp.x, u), readlane_t(sp.y, u)};
+                    if (open && c0 + u != p) tsne_pair<2>(t, s, f, w);
+                }
+                run += n;
+            }
+            if (open && e > b) n_dir += (e - b) - (p >= b && p < e ? 1 : 0);
+        }
+        i = (!leaf && any_open) ? i + 1 : skip;
+    }
+    carry();
+    if (valid) {
+        const int64_t o64 = order[p];
+        const size_t o = (uint64_t)o64 < (uint64_t)N ? (size_t)o64 : 0;
+        part[o] = F[0];
+        part[(size_t)N + o] = F[1];
+        part[2 * (size_t)N + o] = W;
+        if constexpr (VISITS) { visits[2 * o] = n_acc; visits[2 * o + 1] = n_dir; }
+    }
+    const double zsum = block_sum(valid ? W : 0.0, s_red);
+    if (threadIdx.x == 0) zpart[blockIdx.x] = zsum;
+}
+
+// build + traversal: part, zpart of the workspace are what k_tsne_step<2, .> reads with one split
+static int atree_repulsion_launch(const float *Y, const int64_t *order, const int64_t *skeys, int32_t *visits, void *workspace, const ATreePlan &p,
+                                  int64_t N, double angle, hipStream_t s)
+{
+    char *w = (char *)workspace;
+    const int n = (int)N, D = p.D;
+    ATreeHead *head = (ATreeHead *)w;
+    ATreeNode *node = (ATreeNode *)(w + p.node_off);
+    double2 *nsum = (double2 *)(w + p.nsum_off);
+    int *flag = (int *)(w + p.flag_off), *scan = (int *)(w + p.scan_off), *chunk = (int *)(w + p.chunk_off);
+    float2 *ysort = (float2 *)(w + p.ysort_off);
+    hipLaunchKernelGGL(k_atree_flag, dim3(p.nb), dim3(TSNE_TPB), 0, s, skeys, (const float2 *)Y, order, flag, ysort, n, D, p.leaf);
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_atree_scan1, dim3(p.nchunk), dim3(TSNE_TPB), 0, s, flag, scan, chunk, n);
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_atree_scan2, dim3(1), dim3(TSNE_TPB), 0, s, chunk, p.nchunk, head, scan, n, (long long)p.cap);
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_atree_emit, dim3(p.nb), dim3(TSNE_TPB), 0, s, skeys, flag, scan, chunk, p.nchunk, node, n, D, p.leaf, (long long)p.cap);
+    VCY_LAUNCH_CHECK();
+    const int64_t want = (p.cap + TSNE_TPB - 1) / TSNE_TPB;
+    const unsigned g = (unsigned)(want < ATREE_GRID ? want : ATREE_GRID);
+    for (int l = D; l >= 0; --l) {
+        hipLaunchKernelGGL(k_atree_com, dim3(g), dim3(TSNE_TPB), 0, s, node, nsum, ysort, head, n, l);
+        VCY_LAUNCH_CHECK();
+    }
+    const float th2 = (float)(angle * angle);
+    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off);
+    if (visits)
+        hipLaunchKernelGGL(k_tsne_atree_repulsion<true>, dim3(p.tb), dim3(TSNE_TPB), 0, s, node, ysort, order, head, part, zpart, visits, n, th2);
+    else
+        hipLaunchKernelGGL(k_tsne_atree_repulsion<false>, dim3(p.tb), dim3(TSNE_TPB), 0, s, node, ysort, order, head, part, zpart, visits, n, th2);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+static int atree_launch(const float *Y, float *Yout, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
+                        const int64_t *skeys, float *grad, double *update, float *gains, double *stats, void *workspace, int64_t N, int leaf,
+                        int depth, double angle, int compute_error, double momentum, double lr, double min_gain, bool step, hipStream_t s)
+{
+    const ATreePlan p = atree_plan(N, leaf, depth);
+    const int rc = atree_repulsion_launch(Y, order, skeys, nullptr, workspace, p, N, angle, s);
+    if (rc != VCY_OK) return rc;
+    char *w = (char *)workspace;
+    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off), *blk = (double *)(w + p.blk_off);
+    const int n = (int)N;
+    if (step)
+        hipLaunchKernelGGL((k_tsne_step<2, true>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
+                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
+    else
+        hipLaunchKernelGGL((k_tsne_step<2, false>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
+                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
+    VCY_LAUNCH_CHECK();
+    if (compute_error) {
+        hipLaunchKernelGGL(k_tsne_stats, dim3(1), dim3(TSNE_TPB), 0, s, blk, p.nb, stats);
+        VCY_LAUNCH_CHECK();
+    }
+    return VCY_OK;
+}
+
+// the node numbers are int32: N, leaf_size and depth whose bound 1 + 4 depth floor(N / (leaf_size + 1)) does not fit are out of range
+static bool atree_in_range(int64_t N, int leaf, int depth)
+{
+    return N >= 2 && N < (1ll << 30) && leaf >= 1 && depth >= 1 && depth <= ATREE_MAX_DEPTH && atree_cap(N, leaf, depth) < (1ll << 31);
+}
+
+static int atree_check(int64_t N, int n_components, int leaf, int depth, double angle, const char *who)
+{
+    if (n_components != 2) return fail(VCY_ERR_UNSUPPORTED, "%s: the tree repulsion covers n_components == 2 only", who);
+    if (!(N >= 2 && N < (1ll << 30))) return fail(VCY_ERR_INVALID, "%s: N out of range", who);
+    if (leaf < 1) return fail(VCY_ERR_INVALID, "%s: leaf_size must be >= 1", who);
+    if (depth < 1 || depth > ATREE_MAX_DEPTH) return fail(VCY_ERR_INVALID, "%s: max_depth must be 1 .. 24", who);
+    if (!atree_in_range(N, leaf, depth)) return fail(VCY_ERR_INVALID, "%s: the node bound of N, leaf_size and max_depth exceeds 2^31", who);
+    if (!(angle >= 0.0 && angle <= 1.0)) return fail(VCY_ERR_INVALID, "%s: angle must be in [0, 1]", who);
+    return VCY_OK;
+}
+
 }  // namespace vcy
 
 using namespace vcy;
@@ -802,4 +1226,66 @@ extern "C" int vcy_tsne_tree_step(const float *Y, float *Y_out, const int64_t *i
     if (rc != VCY_OK) return rc;
     return tree_launch(Y, Y_out, indptr, indices, pval, order, sorted_keys, nullptr, update, gains, stats, workspace, N, depth, angle,
                        compute_error, momentum, learning_rate, min_gain, true, (hipStream_t)stream);
+}
+
+extern "C" size_t vcy_tsne_atree_workspace_bytes(int64_t N, int leaf_size, int max_depth)
+{
+    if (!atree_in_range(N, leaf_size, max_depth)) return 0;
+    return atree_plan(N, leaf_size, max_depth).bytes;
+}
+
+extern "C" int vcy_tsne_atree_keys(const float *Y, int64_t *keys, void *workspace, int64_t N, int leaf_size, int max_depth, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && keys && workspace, "tsne_atree_keys: null pointer");
+    const int rc = atree_check(N, 2, leaf_size, max_depth, 0.0, "tsne_atree_keys");
+    if (rc != VCY_OK) return rc;
+    const ATreePlan p = atree_plan(N, leaf_size, max_depth);
+    char *w = (char *)workspace;
+    float4 *boxp = (float4 *)(w + p.boxp_off);
+    hipLaunchKernelGGL(k_tree_box, dim3(p.nbx), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, (int)N);
+    VCY_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_atree_keys, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, p.nbx, (ATreeHead *)w, keys, (int)N,
+                       max_depth, leaf_size);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_tsne_atree_repulsion(const float *Y, const int64_t *order, const int64_t *sorted_keys, double *rep, double *Z, int32_t *visits,
+                                        void *workspace, int64_t N, int leaf_size, int max_depth, double angle, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && order && sorted_keys && rep && Z && workspace, "tsne_atree_repulsion: null pointer");
+    const int rc = atree_check(N, 2, leaf_size, max_depth, angle, "tsne_atree_repulsion");
+    if (rc != VCY_OK) return rc;
+    const ATreePlan p = atree_plan(N, leaf_size, max_depth);
+    const int rc2 = atree_repulsion_launch(Y, order, sorted_keys, visits, workspace, p, N, angle, (hipStream_t)stream);
+    if (rc2 != VCY_OK) return rc2;
+    char *w = (char *)workspace;
+    hipLaunchKernelGGL(k_tree_rep_out, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const double *)(w + p.part_off),
+                       (const double *)(w + p.zpart_off), p.tb, rep, Z, (int)N);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_tsne_atree_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
+                                       const int64_t *sorted_keys, float *grad, double *stats, void *workspace, int64_t N, int n_components,
+                                       int leaf_size, int max_depth, double angle, int compute_error, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && indptr && indices && pval && order && sorted_keys && grad && stats && workspace, "tsne_atree_gradient: null pointer");
+    const int rc = atree_check(N, n_components, leaf_size, max_depth, angle, "tsne_atree_gradient");
+    if (rc != VCY_OK) return rc;
+    return atree_launch(Y, nullptr, indptr, indices, pval, order, sorted_keys, grad, nullptr, nullptr, stats, workspace, N, leaf_size, max_depth,
+                        angle, compute_error, 0.0, 0.0, 0.0, false, (hipStream_t)stream);
+}
+
+extern "C" int vcy_tsne_atree_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval,
+                                   const int64_t *order, const int64_t *sorted_keys, double *update, float *gains, double *stats, void *workspace,
+                                   int64_t N, int n_components, int leaf_size, int max_depth, double angle, double momentum, double learning_rate,
+                                   double min_gain, int compute_error, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && Y_out && indptr && indices && pval && order && sorted_keys && update && gains && stats && workspace, "tsne_atree_step: null pointer");
+    VCY_REQUIRE(Y != Y_out, "tsne_atree_step: Y_out must not alias Y (the attraction reads every row's old position)");
+    const int rc = atree_check(N, n_components, leaf_size, max_depth, angle, "tsne_atree_step");
+    if (rc != VCY_OK) return rc;
+    return atree_launch(Y, Y_out, indptr, indices, pval, order, sorted_keys, nullptr, update, gains, stats, workspace, N, leaf_size, max_depth,
+                        angle, compute_error, momentum, learning_rate, min_gain, true, (hipStream_t)stream);
 }

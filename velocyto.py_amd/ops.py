@@ -1827,6 +1827,96 @@ def tsne_tree_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, i
                                              float(min_gain), int(compute_error), _stream()), "tsne_tree_step")
 
 
+TSNE_ATREE_LEAF_SIZE = 32         # default leaf_size of the adaptive tree (DESIGN.md section 9 has the sweep)
+TSNE_ATREE_MAX_DEPTH = 24         # key bits per axis: what a float32 position resolves
+
+
+def tsne_atree_workspace(N: int, leaf_size: int = TSNE_ATREE_LEAF_SIZE, max_depth: int = TSNE_ATREE_MAX_DEPTH) -> torch.Tensor:
+    nbytes = int(_lib.lib().vcy_tsne_atree_workspace_bytes(int(N), int(leaf_size), int(max_depth)))
+    if nbytes == 0:
+        raise ValueError(f"tsne_atree_workspace: N = {N} (>= 2), leaf_size = {leaf_size} (>= 1) or max_depth = {max_depth} (1 .. 24) out of range "
+                         "(or their node bound 1 + 4 max_depth (N // (leaf_size + 1)) does not fit 31 bits)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
+
+
+def _tsne_atree_args(Y: torch.Tensor, ws: torch.Tensor, leaf_size: int, max_depth: int, order: Optional[torch.Tensor] = None,
+                     sorted_keys: Optional[torch.Tensor] = None) -> int:
+    if Y.dim() != 2 or Y.dtype != torch.float32 or not Y.is_contiguous():
+        raise ValueError("t-SNE positions must be a contiguous (N, n_components) float32 device tensor")
+    N = Y.shape[0]
+    need = int(_lib.lib().vcy_tsne_atree_workspace_bytes(N, int(leaf_size), int(max_depth)))
+    if need == 0 or ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError("t-SNE adaptive tree: leaf_size must be >= 1, max_depth 1 .. 24, N >= 2 and the workspace that of "
+                         "tsne_atree_workspace(N, leaf_size, max_depth)")
+    if order is not None and not (order.dtype == torch.int64 and order.numel() == N and order.is_contiguous() and sorted_keys.dtype == torch.int64
+                                  and sorted_keys.numel() == N and sorted_keys.is_contiguous()):
+        raise ValueError("t-SNE adaptive tree: order and sorted_keys must be (N) int64 (tsne_atree_keys)")
+    return N
+
+
+def tsne_atree_keys(Y: torch.Tensor, ws: torch.Tensor, leaf_size: int = TSNE_ATREE_LEAF_SIZE,
+                    max_depth: int = TSNE_ATREE_MAX_DEPTH) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The first half of an adaptive-tree evaluation of positions Y (N, 2) f32: the bounding box goes into the workspace, every
+    point's int64 Morton key of max_depth bits per axis is computed (vcy_tsne_atree_keys) and sorted (torch.sort, stable: plumbing,
+    no host read).  Returns (keys, order, sorted keys), each (N) int64; order, the sorted keys and the same workspace go to
+    tsne_atree_repulsion / tsne_atree_gradient / tsne_atree_step."""
+    N = _tsne_atree_args(Y, ws, leaf_size, max_depth)
+    if Y.shape[1] != 2:
+        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
+    keys = torch.empty(N, dtype=torch.int64, device=Y.device)
+    _lib.check(_lib.lib().vcy_tsne_atree_keys(Y.data_ptr(), keys.data_ptr(), ws.data_ptr(), N, int(leaf_size), int(max_depth), _stream()),
+               "tsne_atree_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    return keys, order, skeys
+
+
+def tsne_atree_repulsion(Y: torch.Tensor, order: torch.Tensor, sorted_keys: torch.Tensor, ws: torch.Tensor, angle: float,
+                         leaf_size: int = TSNE_ATREE_LEAF_SIZE, max_depth: int = TSNE_ATREE_MAX_DEPTH,
+                         visits: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """The Barnes-Hut repulsion on the adaptive tree alone: (rep (N, 3) f64 = force x, y and sum_j w_ij per point, Z (1) f64,
+    visits (N, 2) int32 = accepted nodes and directly summed points per target, or None)."""
+    N = _tsne_atree_args(Y, ws, leaf_size, max_depth, order, sorted_keys)
+    if Y.shape[1] != 2:
+        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
+    rep = torch.empty((N, 3), dtype=torch.float64, device=Y.device)
+    Z = torch.empty(1, dtype=torch.float64, device=Y.device)
+    vis = torch.empty((N, 2), dtype=torch.int32, device=Y.device) if visits else None
+    _lib.check(_lib.lib().vcy_tsne_atree_repulsion(Y.data_ptr(), order.data_ptr(), sorted_keys.data_ptr(), rep.data_ptr(), Z.data_ptr(),
+                                                   vis.data_ptr() if visits else None, ws.data_ptr(), N, int(leaf_size), int(max_depth),
+                                                   float(angle), _stream()), "tsne_atree_repulsion")
+    return rep, Z, vis
+
+
+def tsne_atree_gradient(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
+                        sorted_keys: torch.Tensor, ws: torch.Tensor, angle: float, leaf_size: int = TSNE_ATREE_LEAF_SIZE,
+                        max_depth: int = TSNE_ATREE_MAX_DEPTH, compute_error: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """tsne_gradient with the adaptive-tree repulsion at ``angle`` (0: the exact sum): (grad (N, 2) f32, stats (4) f64)."""
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    _tsne_atree_args(Y, ws, leaf_size, max_depth, order, sorted_keys)
+    grad = torch.empty_like(Y)
+    stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
+    _lib.check(_lib.lib().vcy_tsne_atree_gradient(Y.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), order.data_ptr(),
+                                                  sorted_keys.data_ptr(), grad.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, int(leaf_size),
+                                                  int(max_depth), float(angle), int(compute_error), _stream()), "tsne_atree_gradient")
+    return grad, stats
+
+
+def tsne_atree_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
+                    sorted_keys: torch.Tensor, update: torch.Tensor, gains: torch.Tensor, stats: torch.Tensor, ws: torch.Tensor, angle: float,
+                    momentum: float, learning_rate: float, min_gain: float = 0.01, compute_error: bool = False,
+                    leaf_size: int = TSNE_ATREE_LEAF_SIZE, max_depth: int = TSNE_ATREE_MAX_DEPTH) -> None:
+    """tsne_step with the adaptive-tree repulsion at ``angle``; order and sorted_keys are tsne_atree_keys' of the same Y and workspace."""
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    _tsne_atree_args(Y, ws, leaf_size, max_depth, order, sorted_keys)
+    if not (Y_out.shape == Y.shape and Y_out.dtype == torch.float32 and update.shape == Y.shape and update.dtype == torch.float64
+            and gains.shape == Y.shape and gains.dtype == torch.float32 and stats.numel() >= 4 and stats.dtype == torch.float64):
+        raise ValueError("tsne_atree_step: Y_out (N, 2) f32, update (N, 2) f64, gains (N, 2) f32 and stats (4) f64")
+    _lib.check(_lib.lib().vcy_tsne_atree_step(Y.data_ptr(), Y_out.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(),
+                                              order.data_ptr(), sorted_keys.data_ptr(), update.data_ptr(), gains.data_ptr(), stats.data_ptr(),
+                                              ws.data_ptr(), N, d, int(leaf_size), int(max_depth), float(angle), float(momentum),
+                                              float(learning_rate), float(min_gain), int(compute_error), _stream()), "tsne_atree_step")
+
+
 def select_cells(M, keep) -> "CellMatrix":
     """Cell (row) subset of a cells-major matrix (CellMatrix or CountMatrix)."""
     idx = torch.nonzero(torch.as_tensor(keep, device=M.t.device), as_tuple=False).ravel()

@@ -598,7 +598,7 @@ class PreprocessMixin:
         self.pcsx = self.pcax.fit_transform(self.dev("Sx_norm"))
 
     def perform_TSNE(self, n_dims: int = 2, perplexity: float = 30, initial_pos: np.ndarray = None, theta: float = 0.5, n_pca_dim: int = None,
-                     max_iter: int = 1000, backend: str = "sklearn", repulsion: str = "exact") -> None:
+                     max_iter: int = 1000, backend: str = "sklearn", repulsion: str = "exact", tree_depth=None) -> None:
         """analysis.py:1441-1450: Barnes-Hut t-SNE of the leading PCs -> ``ts`` (cells, n_dims).
 
         backend="sklearn" (the default): scikit-learn, as the reference (its ``n_iter`` keyword is ``max_iter`` since scikit-learn 1.5).
@@ -606,11 +606,12 @@ class PreprocessMixin:
         the gradient is the exact all-pairs one (``theta`` is accepted and ignored: the result is the theta -> 0 limit of
         scikit-learn's); repulsion="tree" (n_dims == 2) honours ``theta`` with scikit-learn's Barnes-Hut acceptance rule, which is what
         atlas sizes need.  The backend keyword is temporary: once the device path's measurements are recorded the default flips to
-        it and the option goes away.  ``repulsion`` is read by the "hip" backend only."""
+        it and the option goes away.  ``repulsion`` and ``tree_depth`` (None, 1 .. 11 or "adaptive": ``DeviceTSNE``'s, for
+        repulsion="tree") are read by the "hip" backend only."""
         if backend == "hip":
             from .tsne import DeviceTSNE
             self.ts = DeviceTSNE(n_components=n_dims, perplexity=perplexity, angle=theta, init="random" if initial_pos is None else initial_pos,
-                                 max_iter=max_iter, repulsion=repulsion).fit_transform(self.pcs[:, :n_pca_dim])
+                                 max_iter=max_iter, repulsion=repulsion, tree_depth=tree_depth).fit_transform(self.pcs[:, :n_pca_dim])
             return
         if backend != "sklearn":
             raise ValueError(f"backend must be 'sklearn' or 'hip', got {backend!r}")

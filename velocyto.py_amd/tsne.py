@@ -13,7 +13,10 @@ Different:
   * by default (``repulsion="exact"``) the repulsion is summed EXACTLY over all pairs, so ``angle`` is accepted and ignored: the
     result is the angle -> 0 limit of scikit-learn's Barnes-Hut gradient, at O(N^2) work per iteration (DESIGN.md section 9);
     ``repulsion="tree"`` (n_components == 2) applies scikit-learn's acceptance rule with ``angle`` on a complete quadtree of fixed
-    depth rebuilt every iteration (scikit-learn's tree is adaptive, so the two accept different nodes at the same angle);
+    depth rebuilt every iteration (scikit-learn's tree is adaptive, so the two accept different nodes at the same angle), or
+    with ``tree_depth="adaptive"`` on a quadtree that, like scikit-learn's, is as deep as the points are dense: a cell is split while
+    it holds more than ``leaf_size`` points, down to the 24 bits per axis a float32 position resolves (scikit-learn splits down to
+    single points; a leaf that is not accepted is summed point by point here);
   * only the point itself is left out of its own repulsion; scikit-learn's tree also drops points that coincide with it within
     its EPSILON (neighbors/_quad_tree.pyx:413-421), so exact duplicates repel each other here;
   * KL, Z and |grad| are summed in f64 (scikit-learn sums the error in f32);
@@ -78,15 +81,17 @@ class DeviceTSNE:
     repulsion: ``"exact"`` (the default) sums the repulsion over all pairs, O(N^2) per iteration; ``angle`` is accepted and IGNORED.
     ``"tree"`` (n_components == 2 only) uses scikit-learn's Barnes-Hut acceptance rule with ``angle`` (0 <= angle <= 1) on a quadtree
     of ``tree_depth`` levels (None: ``ops.tsne_tree_depth(N)``), O(N log N); its iteration is the faster one above about 50 000
-    points (DESIGN.md section 9 has the measurements)."""
+    points (DESIGN.md section 9 has the measurements).  ``tree_depth="adaptive"`` builds the tree to the depth the density asks for
+    instead (cells of more than ``leaf_size`` points are split), so that an iteration costs the same however the points are clumped;
+    ``leaf_size`` (None: ``ops.TSNE_ATREE_LEAF_SIZE``) is read in that mode only."""
 
     _EXPLORATION_MAX_ITER = 250
     _N_ITER_CHECK = 50
 
     def __init__(self, n_components: int = 2, *, perplexity: float = 30.0, early_exaggeration: float = 12.0, learning_rate="auto",
                  max_iter: int = 1000, n_iter_without_progress: int = 300, min_grad_norm: float = 1e-7, init="random", random_state=None,
-                 angle: float = 0.5, repulsion: str = "exact", tree_depth=None):
-        self.repulsion, self.tree_depth = repulsion, tree_depth
+                 angle: float = 0.5, repulsion: str = "exact", tree_depth=None, leaf_size=None):
+        self.repulsion, self.tree_depth, self.leaf_size = repulsion, tree_depth, leaf_size
         self.n_components, self.perplexity, self.early_exaggeration = n_components, perplexity, early_exaggeration
         self.learning_rate, self.max_iter, self.n_iter_without_progress = learning_rate, max_iter, n_iter_without_progress
         self.min_grad_norm, self.init, self.random_state, self.angle = min_grad_norm, init, random_state, angle
@@ -97,7 +102,7 @@ class DeviceTSNE:
             raise ValueError(f"Expected 2D array, got array with shape {tuple(shape)}")
         N = shape[0]
         nc = self.n_components
-        self._check_repulsion(self.repulsion, nc, self.angle, self.tree_depth)
+        self._check_repulsion(self.repulsion, nc, self.angle, self.tree_depth, self.leaf_size)
         if not isinstance(nc, numbers.Integral) or isinstance(nc, bool) or nc < 1:
             raise ValueError(f"The 'n_components' parameter of TSNE must be an int in the range [1, inf). Got {nc!r} instead.")
         if not (isinstance(self.perplexity, numbers.Real) and self.perplexity > 0):
@@ -124,7 +129,7 @@ class DeviceTSNE:
             raise ValueError("'n_components' should be inferior to 4 for the barnes_hut algorithm as it relies on quad-tree or oct-tree.")
 
     @staticmethod
-    def _check_repulsion(repulsion, n_components, angle, tree_depth) -> None:
+    def _check_repulsion(repulsion, n_components, angle, tree_depth, leaf_size=None) -> None:
         if repulsion not in ("exact", "tree"):
             raise ValueError(f"The 'repulsion' parameter of DeviceTSNE must be 'exact' or 'tree'. Got {repulsion!r} instead.")
         if repulsion == "tree":
@@ -132,8 +137,13 @@ class DeviceTSNE:
                 raise NotImplementedError("DeviceTSNE: repulsion='tree' is implemented for n_components == 2 only")
             if not (isinstance(angle, numbers.Real) and 0.0 <= angle <= 1.0):
                 raise ValueError(f"The 'angle' parameter of TSNE must be a float in the range [0.0, 1.0]. Got {angle!r} instead.")
-            if tree_depth is not None and not (isinstance(tree_depth, numbers.Integral) and 1 <= tree_depth <= 11):
-                raise ValueError(f"tree_depth must be None or an int in the range [1, 11]. Got {tree_depth!r} instead.")
+            if isinstance(tree_depth, str):
+                if tree_depth != "adaptive":
+                    raise ValueError(f"tree_depth must be None, 'adaptive' or an int in the range [1, 11]. Got {tree_depth!r} instead.")
+                if leaf_size is not None and not (isinstance(leaf_size, numbers.Integral) and not isinstance(leaf_size, bool) and leaf_size >= 1):
+                    raise ValueError(f"leaf_size must be None or an int in the range [1, inf). Got {leaf_size!r} instead.")
+            elif tree_depth is not None and not (isinstance(tree_depth, numbers.Integral) and 1 <= tree_depth <= 11):
+                raise ValueError(f"tree_depth must be None, 'adaptive' or an int in the range [1, 11]. Got {tree_depth!r} instead.")
 
     def fit_transform(self, X, y=None) -> np.ndarray:
         """X: (n_samples, n_features) host array or device tensor.  Returns the embedding (n_samples, n_components) float32."""
@@ -189,13 +199,19 @@ class DeviceTSNE:
         """_gradient_descent (_t_sne.py:301-444) from positions Y (N, d) f32 on the device: fresh update and gains, one vcy_tsne_step
         per iteration on one stream; the host reads back [Z, KL, |grad|^2] only where scikit-learn computes the error (every 50th
         iteration and the last).  Returns (positions, error, last iteration).
-        repulsion="tree": per iteration the keys, their sort and vcy_tsne_tree_step; the read at a check also carries whether the
-        new positions are finite, and a fit whose positions are not stops there with a FloatingPointError."""
+        repulsion="tree": per iteration the keys, their sort and vcy_tsne_tree_step (tree_depth="adaptive": vcy_tsne_atree_step); the
+        read at a check also carries whether the new positions are finite, and a fit whose positions are not stops there with a
+        FloatingPointError."""
         indptr, indices, pval = csr
         N, d = Y.shape
         tree = self.repulsion == "tree"
+        adaptive = tree and isinstance(self.tree_depth, str)
         if tree:
-            self._check_repulsion(self.repulsion, d, self.angle, self.tree_depth)
+            self._check_repulsion(self.repulsion, d, self.angle, self.tree_depth, self.leaf_size)
+        if adaptive:
+            leaf = self._leaf_size(self.leaf_size)
+            tws = ops.tsne_atree_workspace(N, leaf)
+        elif tree:
             depth = ops.tsne_tree_depth(N) if self.tree_depth is None else int(self.tree_depth)
             tws = ops.tsne_tree_workspace(N, depth)
         update = torch.zeros((N, d), dtype=torch.float64, device=Y.device)
@@ -209,7 +225,11 @@ class DeviceTSNE:
         for i in range(it, max_iter):
             check = (i + 1) % self._N_ITER_CHECK == 0
             want = check or i == max_iter - 1
-            if tree:
+            if adaptive:
+                _, order, skeys = ops.tsne_atree_keys(Y, tws, leaf)
+                ops.tsne_atree_step(Y, Y_next, indptr, indices, pval, order, skeys, update, gains, stats, tws, self.angle, momentum, lr, 0.01,
+                                    want, leaf_size=leaf)
+            elif tree:
                 _, order, skeys = ops.tsne_tree_keys(Y, tws, depth)
                 ops.tsne_tree_step(Y, Y_next, indptr, indices, pval, order, skeys, update, gains, stats, tws, depth, self.angle, momentum, lr,
                                    0.01, want)
@@ -243,11 +263,21 @@ class DeviceTSNE:
                torch.from_numpy(np.asarray(P.data, dtype=np.float32)).to(dev))
         return Yd, csr
 
-    def _objective(self, Y, P, repulsion: str = "exact", angle: float = 0.5, tree_depth=None) -> Tuple[float, np.ndarray]:
+    @staticmethod
+    def _leaf_size(leaf_size) -> int:
+        return ops.TSNE_ATREE_LEAF_SIZE if leaf_size is None else int(leaf_size)
+
+    def _objective(self, Y, P, repulsion: str = "exact", angle: float = 0.5, tree_depth=None, leaf_size=None) -> Tuple[float, np.ndarray]:
         """(KL, grad (N, d) f32) for positions Y and a scipy CSR P (its values read as f32): of _kl_divergence_bh at angle = 0
-        (repulsion="exact"), or with the tree repulsion at ``angle`` (repulsion="tree")."""
+        (repulsion="exact"), or with the tree repulsion at ``angle`` (repulsion="tree"; tree_depth="adaptive": the adaptive tree)."""
         Yd, csr = self._device_args(Y, P)
-        self._check_repulsion(repulsion, Yd.shape[1], angle, tree_depth)
+        self._check_repulsion(repulsion, Yd.shape[1], angle, tree_depth, leaf_size)
+        if repulsion == "tree" and isinstance(tree_depth, str):
+            leaf = self._leaf_size(leaf_size)
+            tws = ops.tsne_atree_workspace(Yd.shape[0], leaf)
+            _, order, skeys = ops.tsne_atree_keys(Yd, tws, leaf)
+            grad, stats = ops.tsne_atree_gradient(Yd, *csr, order, skeys, tws, angle, leaf_size=leaf, compute_error=True)
+            return float(stats[1]), grad.cpu().numpy()
         if repulsion == "tree":
             depth = ops.tsne_tree_depth(Yd.shape[0]) if tree_depth is None else int(tree_depth)
             tws = ops.tsne_tree_workspace(Yd.shape[0], depth)
