@@ -47,9 +47,14 @@ typedef enum {
     VCY_RULES_FULL = 0,
     /* The partial rule of speedboosted.pyx:372-378: A = sign(t) sqrt(|t| + psc), 0 below |t| = 1e-16.  What it guarantees about the root:
      * VCY_F32 and the other transforms: the unit's own root / logarithm.  VCY_SQRT on VCY_F64 in the vcy_coldeltacor_partial* entries: the
-     * f32-seeded root after ONE Newton correction, relative error of A at most 2^-44 (a priori 3.7 2^-46; the largest over 2^26 arguments
-     * in [2^-60, 2^60] is 2^-45.46, 179 ulps, mean 10 ulps: profiles/r07_valu_issue_f64.txt; the tests hold it to 2^-43.5); a pair's correlation moves by at most 2 x that x sqrt(sum A^2 / sum (A - mean A)^2) against the
-     * correctly rounded root - 2e-13 on count data, under the rounding of the G-term sums.  16 instructions per gene instead of 18.          */
+     * f32-seeded root after ONE Newton step, relative error of A at most 2^-44 (a priori 1.5 (2^-23 + 2^-25)^2 + 3 2^-53 = 2^-44.7, always on
+     * the low side; measured over 2^26 arguments in [2^-60, 2^60]: profiles/r09_valu_issue_f64.txt; tests/test_gpu_cdc_root_scaled.py holds the
+     * element to the a-priori figure, tests/test_gpu_cdc_root.py to 2^-43.5); a pair's correlation moves by at most 2 x that x sqrt(sum A^2 / sum (A - mean A)^2) against the
+     * correctly rounded root - 2e-13 on count data, under the rounding of the G-term sums.  The step is taken in its reciprocal-root form and
+     * yields 2 sqrt(|t| + psc): inside the kernels the f64 partial-sqrt moments are those of 2 A (sum A and sum A b twice, sum A^2 four times
+     * what the rule states).  They never leave the kernel, and cov / sqrt(var_A var_b) is formed from exact power-of-two multiples rounded at
+     * the same places, so r is bit for bit what the same roots unscaled would give.  13 instructions per gene in the grouped kernels (14 in
+     * the one-cell-per-workgroup kernel) instead of 18.                                                                                      */
     VCY_RULES_PARTIAL = 1,
     /* The partial rule with the pseudocount dropped: A = sign(t) sqrt|t| (0 at t == 0).  VCY_SQRT on VCY_F32 matrices in the
      * vcy_coldeltacor_partial* entries only (anything else: VCY_ERR_INVALID).  In f32 `|t| + psc` rounds to `|t|` for every

@@ -127,8 +127,23 @@ __device__ __forceinline__ double sqrt_seedzero1(double x, bool discard)  // rou
     const double d = fma(-s0, s0, x);
     return fma(d, h, s0);
 }
+__device__ __forceinline__ double rsqrt2_seedzero(double x, bool discard)  // round 9 (the kernel's VCY_RULES_PARTIAL element): 2 sqrt(x) by ONE Newton step in its rsqrt form on the one
+{                                                                          // seed Y = rsq((float)x): u = x Y, w = 3 - u Y, u w - no halving, no second seed; the zero rule on the seed's
+    const float xf0 = (float)x;                                            // argument gives Y = 0, u = 0, w = 3: an exact 0.  14 instructions per element
+    const float xf = discard ? __builtin_inff() : xf0;
+    const double y = (double)__builtin_amdgcn_rsqf(xf);
+    const double u = x * y;
+    return u * fma(-u, y, 3.0);
+}
+__device__ __forceinline__ double rsqrt2_seed(double x)                    // the same without the rule (the masked element's root: 13 instructions per element)
+{
+    const double y = (double)__builtin_amdgcn_rsqf((float)x);
+    const double u = x * y;
+    return u * fma(-u, y, 3.0);
+}
 template <int MODE> __device__ __forceinline__ double elem(double t, double psc)
 {
+    if (MODE == 8) return copysign(rsqrt2_seedzero(fabs(t) + psc, fabs(t) < 1e-16), t);
     if (MODE == 7) return copysign(sqrt_seedzero1(fabs(t) + psc, fabs(t) < 1e-16), t);
     if (MODE == 5) return copysign(sqrt_seedzero(fabs(t) + psc, fabs(t) < 1e-16), t);
     if (MODE == 6) return copysign(sqrt_seedzero_f64prod(fabs(t) + psc, fabs(t) < 1e-16), t);
@@ -172,7 +187,7 @@ __device__ __forceinline__ double sqrt_seed1(double x)                     // sq
     const double d = fma(-s0, s0, x);
     return fma(d, h, s0);
 }
-template <bool ABS2>
+template <bool ABS2, bool SCALED = false>                   // SCALED (round 9): the root is rsqrt2_seed, A' = 2 sign(t) sqrt(x)
 __global__ void __launch_bounds__(256) k_elem_masked(double *out, unsigned long long *cyc, double seed)
 {
     constexpr int NE = 4;
@@ -185,7 +200,7 @@ __global__ void __launch_bounds__(256) k_elem_masked(double *out, unsigned long 
         for (int k = 0; k < NE; ++k) {
             const double t = x[k] - e[k];
             if (!(fabs(t) < 1e-16)) {
-                const double a = copysign(sqrt_seed1(fabs(t) + psc), t);
+                const double a = copysign(SCALED ? rsqrt2_seed(fabs(t) + psc) : sqrt_seed1(fabs(t) + psc), t);
                 sA[k & 1] += a;
                 sAA[k & 1] = ABS2 ? sAA[k & 1] + (fabs(t) + psc) : fma(a, a, sAA[k & 1]);
                 sAb[k & 1] = fma(a, b[k], sAb[k & 1]);
@@ -249,6 +264,33 @@ __global__ void k_sqrt_err1(double *maxrel, unsigned long long *cnt, int n)
     atomicAdd(&cnt[3], bad0);
 }
 
+// round 9: half the scaled root (an exact halving) against sqrt() over the same sweep, the same figures; the masked form's root (no rule) must be
+// the select form's bit for bit
+__global__ void k_sqrt_err2(double *maxrel, unsigned long long *cnt, int n)
+{
+    double m = 0;
+    unsigned long long ulpmax = 0, ulpsum = 0, off = 0, bad0 = 0, high = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const double x = exp2(-60.0 + 120.0 * (double)i / n) * (1.0 + 1e-3 * (i % 997));
+        const double s = sqrt(x), q = 0.5 * rsqrt2_seedzero(x, false);
+        m = fmax(m, fabs(q - s) / s);
+        const long long du = __double_as_longlong(q) - __double_as_longlong(s);
+        const unsigned long long au = (unsigned long long)(du < 0 ? -du : du);
+        ulpmax = au > ulpmax ? au : ulpmax;
+        ulpsum += au;
+        off += q != s;
+        high += du > 1;                                                    // the error is on the low side: nothing above sqrt() but its rounding
+        bad0 += rsqrt2_seedzero(x, true) != 0.0;
+        bad0 += (0.5 * rsqrt2_seed(x) != q) ? (1ull << 40) : 0ull;
+    }
+    atomicMax((unsigned long long *)maxrel, (unsigned long long)__double_as_longlong(m));
+    atomicMax(&cnt[0], ulpmax);
+    atomicAdd(&cnt[1], ulpsum);
+    atomicAdd(&cnt[2], off);
+    atomicAdd(&cnt[3], bad0);
+    atomicAdd(&cnt[4], high);
+}
+
 template <typename F> static void run(const char *name, F k, int wps, double units_per_iter, const char *unit)
 {
     hipDeviceProp_t p; hipGetDeviceProperties(&p, 0);
@@ -283,6 +325,8 @@ int main()
     run("f64 element, zero rule on the seed's argument, ONE Newton correction (round 7: VCY_RULES_PARTIAL)", k_elem<7>, w, 4, "element");
     run("f64 element, zero rule as an execution mask, ONE Newton correction (round 8)", k_elem_masked<false>, w, 4, "element");
     run("f64 element, the same with sum A^2 as sum (|t| + psc) over the kept elements (round 8)", k_elem_masked<true>, w, 4, "element");
+    run("f64 element, 2 sqrt(x) by one rsqrt-form Newton step, zero rule on the seed's argument (round 9: k_cdc_partial's)", k_elem<8>, w, 4, "element");
+    run("f64 element, the same root under the execution mask (round 9: the grouped kernel's VCY_RULES_PARTIAL)", k_elem_masked<false, true>, w, 4, "element");
     run("f64 element, library sqrt()", k_elem<3>, w, 4, "element");
     double *mr; hipMalloc(&mr, 48); hipMemset(mr, 0, 48);
     k_sqrt_err<<<1024, 256>>>(mr, 1 << 26);
@@ -296,5 +340,11 @@ int main()
     double hm; unsigned long long hc[4]; hipMemcpy(&hm, m1, 8, hipMemcpyDeviceToHost); hipMemcpy(hc, c1, 32, hipMemcpyDeviceToHost);
     printf("one Newton correction (round 7) against sqrt() over the same 2^26 arguments: max relative error %.4g = 2^%.2f; distance in ulps of the result: max %llu, "
            "mean %.1f; %llu results not equal to sqrt() bit for bit; %llu discarded elements not an exact 0\n", hm, log2(hm), hc[0], (double)hc[1] / (1 << 26), hc[2], hc[3]);
+    double *m2; unsigned long long *c2; hipMalloc(&m2, 8); hipMalloc(&c2, 40); hipMemset(m2, 0, 8); hipMemset(c2, 0, 40);
+    k_sqrt_err2<<<1024, 256>>>(m2, c2, 1 << 26);
+    unsigned long long hd[5]; hipMemcpy(&hm, m2, 8, hipMemcpyDeviceToHost); hipMemcpy(hd, c2, 40, hipMemcpyDeviceToHost);
+    printf("half the scaled root of one rsqrt-form Newton step (round 9) against sqrt() over the same 2^26 arguments: max relative error %.4g = 2^%.2f; distance in ulps of "
+           "the result: max %llu, mean %.1f; %llu results not equal to sqrt() bit for bit, %llu more than one ulp ABOVE it; %llu discarded elements not an exact 0 "
+           "(2^40 x the masked form's roots that are not the select form's would show here)\n", hm, log2(hm), hd[0], (double)hd[1] / (1 << 26), hd[2], hd[4], hd[3]);
     return 0;
 }

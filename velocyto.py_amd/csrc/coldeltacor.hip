@@ -109,7 +109,8 @@ template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_
     return copysign(fma(d, h, s1), t);
 }
 
-// VCY_RULES_PARTIAL, the default f64 element: the same seed, zero rule and sign with ONE Newton correction - 16 instructions per element
+// VCY_RULES_PARTIAL, the default f64 element.  Rounds 7 and 8 (the form the next paragraph replaces, kept here for its figures): the same seed,
+// zero rule and sign with ONE Newton correction - 16 instructions per element
 // (15 in the grouped kernel, where the zero rule is an execution mask: ZeroMasked<> / xform_kept below; this form serves k_cdc_partial),
 // the second `d = x - s1^2`, `s1 + d h` pair (two v_fma_f64) left out.  Error of the root after the one correction, relative: with e0 the
 // error of the 24-bit seed s0 (the rounding of x to f32, 2^-24, half of it reaching the root; v_rsq_f32, 1 ulp; the rounding of the f32 product
@@ -119,16 +120,33 @@ template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_
 // element at 70.6 clocks against 77.4 (profiles/r07_valu_issue_f64.txt); stage D 205.6 against 230.5 ms in one call (profiles/r07_root1_vs_root2.txt).
 // Pearson's r of a pair moves by |dr| <= 2 delta sqrt(sum A^2 / sum (A - mean A)^2) for a relative element error delta (Cauchy-Schwarz, as in
 // ops.partial_rules_for): 2e-13 at delta = 2^-44 and the ratios of pooled count data (<= 2.5), 500 times below the f64 bar of 1e-10 and below the
-// a-priori bound of the G-term f64 accumulation itself.  VCY_RULES_PARTIAL_ROOT2 (below) keeps the two-correction root.
+// a-priori bound of the G-term f64 accumulation itself.  VCY_RULES_PARTIAL_ROOT2 (above) keeps the two-correction root.
+//
+// Round 9: the SCALED root.  The sqrt form of Newton's step needs two seeds, s0 and h = 1 / (2 s0): two v_mul_f32 and one conversion exist
+// only to put the 1/2 somewhere.  The element of VCY_RULES_PARTIAL therefore returns A' = 2 sign(t) sqrt(x), for which the rsqrt form of the
+// step needs the one seed Y = (double)v_rsq_f32((float)x) and no halving:
+//     u = x Y  (~ sqrt x),   w = 3 - u Y  (v_fma_f64, the 3.0 in a scalar register pair),   A' = copysign(u w, t)  = 2 sqrt(x) (1 - 1.5 e^2 - 0.5 e^3)
+// for Y = (1 + e) / sqrt x - six instructions (cvt, rsq, cvt, v_mul_f64, v_fma_f64, v_mul_f64) where the form above takes eight; with sub, add,
+// the compare, v_bfi and the three moment updates the element is 13 vector instructions in the grouped kernel (14 here, with the v_cndmask).
+// THE MOMENTS OF THE f64 PARTIAL-SQRT INSTANCES ARE THOSE OF 2 A.  Every caller of this specialisation and of xform_kept<VCY_RULES_PARTIAL> uses
+// the value for sum A, sum A^2, sum A b [, sum A b2] of one pair and nothing else (xform_s in k_cdc_partial's loops, fold in the grouped
+// kernel; Shifted<> is false here, so no K of another scale is subtracted), and the sums never leave the kernel: sum A and sum A b carry a
+// factor 2, sum A^2 a factor 4, cov = sAb - sA sb / n a 2, va = sAA - sA^2 / n a 4, sqrt(va vb) a 2 - every one an exact power-of-two
+// multiple of what the unscaled roots 0.5 A' would give, rounded at the same places, so cov / sqrt(va vb) is the same bits.
+// Error, relative, always on the low side: |e| <= 2^-23 + 2^-25 (v_rsq_f32 to one ulp; the rounding of x to f32, half of which reaches the
+// seed); the rounding of u enters the residual absolutely (2^-53), the fma and the last product add 2^-53 each:
+// 1.5 (1.25 2^-23)^2 + 3 2^-53 = 2.4 2^-46 = 2^-44.7 a priori (the form above: 3.7 2^-46), under the 2^-44 of include/velocyto_hip.h;
+// tools/ubench/valu_issue_f64.hip measures 2^-45.66 at most over 2^26 arguments (154 ulps, mean 9.7: profiles/r09_valu_issue_f64.txt).
+// Zero rule: v_rsq_f32(+inf) = +0 gives Y = 0, u = x 0 = 0, w = 3 and an exact A' = +-0; a NaN or infinite t gives NaN as before; the domain
+// (x inside the f32 exponent range) is unchanged and 4 x <= 1.4e39 is nothing to an f64 sum.  Measured: profiles/stage_d_root_rsqrt.txt.
 template <> __device__ __forceinline__ double xform<double, VCY_SQRT, VCY_RULES_PARTIAL>(double t, double psc)
 {
     const double x = fabs(t) + psc;
     const float xf0 = (float)x;
     const float xf = (fabs(t) < 1e-16) ? __builtin_inff() : xf0;
-    const float yf = __builtin_amdgcn_rsqf(xf);
-    const double s0 = (double)(xf0 * yf), h = (double)(0.5f * yf);
-    const double d = fma(-s0, s0, x);
-    return copysign(fma(d, h, s0), t);
+    const double y = (double)__builtin_amdgcn_rsqf(xf);
+    const double u = x * y;
+    return copysign(u * fma(-u, y, 3.0), t);
 }
 
 // VCY_RULES_PARTIAL_NOPSC (f32, sqrt): A = sign(t) sqrt|t| as t * rsq|t| with the legacy multiply (0 * anything = 0: the zero
@@ -156,8 +174,11 @@ template <int TR, int RULES> struct Shifted { static constexpr bool value = TR =
 // Zero rule as an execution mask (the grouped kernel's f64 partial-sqrt elements only).  A discarded element (|t| < 1e-16) adds nothing to
 // sum A, sum A^2 or sum A b, so instead of selecting a zero root (v_cmp_f64 + v_cndmask_b32 on the seed's argument, then three moment updates
 // that add the zero) the compare switches the lane off for the rest of the element: v_cmp_nlt_f64 + s_and_saveexec_b64 [+ s_cbranch_execz] +
-// s_or_b64 - the select moves from the vector ALU to the scalar unit, 15 vector instructions per element instead of 16.  xform_kept is the
-// element of a lane that stays on: the root of xform<double, VCY_SQRT, RULES> with the seed taken from (float)x directly.  Kept elements get
+// s_or_b64 - the select moves from the vector ALU to the scalar unit, one vector instruction fewer per element (15 for 16 in round 8, 13 for 14
+// with the scaled root).  xform_kept is the
+// element of a lane that stays on: the root of xform<double, VCY_SQRT, RULES> with the seed taken from (float)x directly - for VCY_RULES_PARTIAL
+// the scaled root 2 sign(t) sqrt(x) of that specialisation (the moments are those of 2 A, see there), for VCY_RULES_PARTIAL_ROOT2 the
+// two-correction root and the unscaled A.  Kept elements get
 // the values they had, discarded ones added +-0: sums and results are the same bits (a NaN t is kept, as under `(|t| < 1e-16) ? 0 : ...`;
 // a NaN or inf in d[c] at a discarded gene no longer reaches sum A b as 0 * NaN, the result is NaN all the same through sum b).
 template <typename T, int TR, int RULES> struct ZeroMasked {
@@ -168,14 +189,17 @@ template <int RULES> __device__ __forceinline__ double xform_kept(double t, doub
     const double x = fabs(t) + psc;
     const float xf = (float)x;
     const float yf = __builtin_amdgcn_rsqf(xf);
-    const double s0 = (double)(xf * yf), h = (double)(0.5f * yf);
-    double d = fma(-s0, s0, x);
-    double s = fma(d, h, s0);
-    if (RULES == VCY_RULES_PARTIAL_ROOT2) {                      // the second Newton correction
-        d = fma(-s, s, x);
-        s = fma(d, h, s);
+    if constexpr (RULES == VCY_RULES_PARTIAL_ROOT2) {            // two Newton corrections in the sqrt form, unscaled
+        const double s0 = (double)(xf * yf), h = (double)(0.5f * yf);
+        double d = fma(-s0, s0, x);
+        const double s1 = fma(d, h, s0);
+        d = fma(-s1, s1, x);
+        return copysign(fma(d, h, s1), t);
+    } else {                                                     // one step in the rsqrt form: 2 sqrt(x)
+        const double y = (double)yf;
+        const double u = x * y;
+        return copysign(u * fma(-u, y, 3.0), t);
     }
-    return copysign(s, t);
 }
 
 template <typename T, int TR, int RULES> __device__ __forceinline__ T xform_shift(T psc)

@@ -719,7 +719,8 @@ def partial_rules_for(e: CellMatrix, transform: int, psc: float, stats: Optional
       * no non-zero |e| below 1e-20: v_rsq_f32 reads a denormal as zero, so t * rsq|t| of a difference below 2^-126 would be
         inf; differences of entries at or above 1e-20 are multiples of their ulp (> 1e-27) and stay in the normal range.
     On an f64 matrix with the sqrt transform the choice is between two roots of the same rule: RULES_PARTIAL, whose root carries one
-    Newton correction (relative error of A at most 2^-44, measured 2^-45.46; 16 instructions per gene), and - under `literal=True` or
+    Newton step (relative error of A at most 2^-44, a priori 2^-44.7; 13 instructions per gene in the grouped kernels - the step is taken in
+    its reciprocal-root form and the kernel's moments are those of 2 A, which leaves r the same bits: include/velocyto_hip.h), and - under `literal=True` or
     VELOCYTO_AMD_LITERAL_RULE=1 - RULES_PARTIAL_ROOT2, the two-correction root (correctly rounded except near ties; 18 instructions).
     `stats`: a precomputed abs_stats vector - sharded callers all-reduce it (sum, min, sum) so that every rank decides alike
     (distributed.all_reduce_abs_stats); `cells`: the number of cells the sums cover when it is not e.C.  `literal=True` or
