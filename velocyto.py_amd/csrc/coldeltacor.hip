@@ -21,7 +21,10 @@
 #ifndef VCY_EXP
 #define VCY_EXP 0
 #endif
+#include <map>
+#include <mutex>
 #include <type_traits>
+#include <utility>
 
 namespace vcy {
 
@@ -445,7 +448,7 @@ template <typename T> __host__ __device__ inline size_t grouped_lds_bytes(int gc
 {
     const int as = dual ? 4 : 3;
     return (size_t)(dual ? 3 : 2) * gc * nv * 64 * 16 + (size_t)npad * 8 + sizeof(T) * (size_t)as * ((maxpairs + 1) & ~(int64_t)1) +
-           8 * (size_t)(maxpairs + 2 > 64 + 4 * gc ? maxpairs + 2 : 64 + 4 * gc) + (size_t)(gc + 18) * sizeof(int) + 16;
+           8 * (size_t)(maxpairs + 2 > 64 + 4 * gc ? maxpairs + 2 : 64 + 4 * gc) + (size_t)(gc + 19) * sizeof(int) + 16;
 }
 
 // K lane-vectors of a chunk are evaluated; full: the chunk is a whole one (K == NV, rows loaded without predicates)
@@ -460,12 +463,24 @@ template <int K, int NV, typename F> __device__ __forceinline__ void for_even_co
         f(RowVecs<K, false>{});
 }
 
+// Arguments of the grouped kernel, one struct = the kernel-argument segment.  The kernel is a loop over units and reads the fields it
+// needs at the top of every unit, through a pointer the compiler cannot see through: otherwise all of them stay in scalar registers
+// across the row loop, which has none to spare (the first form of the unit loop spilled ~60 SGPRs and, through the VGPRs that took
+// them, 52 - 188 bytes of scratch per lane in the f64 instances).
+template <typename T> struct GroupedArgs {
+    const T *e, *d, *d2;
+    const int32_t *ixs;
+    T *out, *out2;
+    const int32_t *order;
+    unsigned *queue;                                            // the eight list heads
+    int64_t ld, cell0, d_row0;
+    int G, C_main, tile_main, C_tail, tile_tail, nrndm_all, stride, npad, nunits;
+    T psc;
+    FuseArgs<T> fuse;
+};
+
 template <typename T, int TR, int RULES, int GC, int NV, bool DUAL>
-__global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restrict__ e, const T *__restrict__ d, const T *__restrict__ d2,
-                                                               const int32_t *__restrict__ ixs, T *__restrict__ out, T *__restrict__ out2,
-                                                               const int32_t *__restrict__ order, int G, int64_t ld, int64_t cell0,
-                                                               int64_t d_row0, int C_main, int tile_main, int C_tail, int tile_tail, int nrndm_all, int stride, int npad, T psc,
-                                                               FuseArgs<T> fuse)
+__global__ __launch_bounds__(1024) void k_cdc_partial_grouped(GroupedArgs<T>)
 {
     using V = typename Vec<T>::type;
     constexpr int N = Vec<T>::N;
@@ -473,6 +488,35 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
     constexpr int AS = DUAL ? 4 : 3;                            // running moments per pair: sum A, sum A^2, sum A b [, sum A b2]
     constexpr int PW = DUAL ? 4 : 2;                            // d-moment partials per wave
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // The launch is one PERSISTENT workgroup per CU (LDS admits no second one) and a queue of units.  A unit is what a block of the
+    // launch used to be - a (group, column tile), main part or tail part - and keeps that block's number: XCD x owns the units
+    // u = 8 q + x, q = 0, 1, ..., which are the groups [x*per, (x+1)*per) of every tile in turn (groups that share neighbour rows share
+    // one L2) and end with the narrow pieces of the tail part.  queue[x] is the head of XCD x's list: a workgroup draws from the list of
+    // the XCD it runs on (hardware id register: speed only, any value is correct) by one fetch-add from a vector lane, and when that list
+    // is exhausted from the list with most units left.  The XCDs run at different clocks under this kernel (1 - 2 % apart) and the groups
+    // differ in rows: with equal static shares the launch ended with the slowest XCD.  No workgroup ever waits for another; a counter
+    // that is overshot stays exhausted.  The host zeroes the eight counters in-stream before the launch.
+    // One launch, two parts.  Main part: the first C_main cells of the schedule, neighbour lists (nrndm_all columns, row
+    // pitch `stride`) in column tiles of tile_main.  Tail part: the C_tail cells after them - the groups beyond the last
+    // full round of the device - in narrower tiles of tile_tail, so that the units handed out last are short ones.
+    // unit -> (group, tile); the tiles of one group are gblocks apart.
+    typedef const GroupedArgs<T> __attribute__((address_space(4))) *ArgPtr;
+    ArgPtr ka = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  for (;;) {
+    // (what a unit derives from the arguments, the thread number and the block size is derived again in every unit: hoisted out of this
+    //  loop it would all stay in registers across the row loop, which has none to spare - see GroupedArgs)
+    int tid = threadIdx.x, nthr = blockDim.x;
+    asm volatile("" : "+s"(ka), "+v"(tid), "+s"(nthr));
+    const int lane = tid & 63, wave = tid >> 6, nwaves = nthr >> 6;
+    const T *__restrict__ e = ka->e, *__restrict__ d = ka->d, *__restrict__ d2 = ka->d2;
+    const int32_t *__restrict__ ixs_all = ka->ixs, *__restrict__ order = ka->order;
+    T *__restrict__ out_all = ka->out, *__restrict__ out2_all = ka->out2;
+    unsigned *__restrict__ queue = ka->queue;
+    const int64_t ld = ka->ld, cell0 = ka->cell0, d_row0 = ka->d_row0;
+    const int G = ka->G, C_main = ka->C_main, tile_main = ka->tile_main, C_tail = ka->C_tail, tile_tail = ka->tile_tail;
+    const int nrndm_all = ka->nrndm_all, stride = ka->stride, npad = ka->npad;
+    const T psc = ka->psc;
+    const FuseArgs<T> fuse{ka->fuse.Ux, ka->fuse.gamma, ka->fuse.q, ka->fuse.dt_shift, ka->fuse.used_dt};
     const int maxpairs = GC * max(tile_main, tile_tail);        // LDS layout is sized for the widest tile
     T *ec = reinterpret_cast<T *>(smem);                        // [GC][GCHUNK]
     T *dc = ec + GC * GCHUNK;                                   // [GC][GCHUNK]
@@ -489,34 +533,52 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
     int *s_wavetot = s_cells + GC;                              // [16]
     int &s_U = s_wavetot[16];
     int *s_next = s_wavetot + 17;                               // dynamic row counter
+    int *s_unit = s_wavetot + 18;                               // the unit this workgroup drew from the queue
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    // XCD-aware schedule: workgroup b runs on XCD b % 8 (observed; speed only) -> XCD x owns the contiguous
-    // range of groups [x*per, (x+1)*per), so groups that share neighbour rows share one L2
-    // One launch, two parts.  Main part: the first C_main cells of the schedule, neighbour lists (nrndm_all columns, row
-    // pitch `stride`) in column tiles of tile_main.  Tail part: the C_tail cells after them - the groups beyond the last
-    // full round of the device - in narrower tiles of tile_tail, so that the blocks dispatched last are short ones.
-    // block -> (group, tile); the tiles of one group are gblocks apart.
     const int nb_main = ((((C_main + GC - 1) / GC) + 7) / 8 * 8) * (C_main > 0 ? (nrndm_all + tile_main - 1) / tile_main : 0);
-    const bool tail = (int)blockIdx.x >= nb_main;
-    const int bx = tail ? (int)blockIdx.x - nb_main : (int)blockIdx.x;
+    const int xcd = (int)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u);     // hwreg(HW_REG_XCC_ID, 0, 4)
+    const int qlen = ka->nunits >> 3;                           // units per XCD list (nunits is a multiple of 8)
+    __syncthreads();                                            // the last unit's epilogue is through with keys, acc, s_cells (and s_unit)
+    if (tid == 0) {
+        int u = -1;
+        unsigned q = __hip_atomic_fetch_add(&queue[xcd], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (q < (unsigned)qlen) u = 8 * (int)q + xcd;
+        else
+            for (;;) {                                          // every failed draw leaves its list exhausted for good: at most 8 rounds
+                int best = -1, left = 0;
+                for (int y = 0; y < 8; ++y) {
+                    const unsigned h = __hip_atomic_load(&queue[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const int l = h < (unsigned)qlen ? qlen - (int)h : 0;
+                    if (l > left) { left = l; best = y; }
+                }
+                if (best < 0) break;
+                q = __hip_atomic_fetch_add(&queue[best], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (q < (unsigned)qlen) { u = 8 * (int)q + best; break; }
+            }
+        *s_unit = u;
+    }
+    __syncthreads();
+    const int unit = *s_unit;
+    if (unit < 0) break;
+    const bool tail = unit >= nb_main;
+    const int bx = tail ? unit - nb_main : unit;
     const int C_out = tail ? C_tail : C_main, pos0 = tail ? C_main : 0, tilew = tail ? tile_tail : tile_main;
     const int ngroups = (C_out + GC - 1) / GC, per = (ngroups + 7) / 8, gblocks = per * 8;
     const int tile = bx / gblocks, bg = bx - tile * gblocks;
     const int gpos = (bg & 7) * per + (bg >> 3);
-    if (gpos >= ngroups) return;
+    if (gpos >= ngroups) continue;
     const int n0 = tile * tilew;
     const int nrndm = min(tilew, nrndm_all - n0);
-    ixs += n0;
-    out += n0;
-    if (DUAL) out2 += n0;
+    const int32_t *__restrict__ ixs = ixs_all + n0;
+    T *__restrict__ out = out_all + n0;
+    T *__restrict__ out2 = DUAL ? out2_all + n0 : nullptr;
     const int g0cell = gpos * GC;
     const int gcount = min(GC, C_out - g0cell);
     const int npairs = gcount * nrndm;
     if (tid < GC) s_cells[tid] = tid < gcount ? (order ? order[pos0 + g0cell + tid] : pos0 + g0cell + tid) : 0;
     __syncthreads();
     // ---- 1. keys = (neighbour << 16) | (member << 12) | slot, sorted
-    for (int t = tid; t < npad; t += blockDim.x) {
+    for (int t = tid; t < npad; t += nthr) {
         unsigned long long key = ~0ull;
         if (t < npairs) {
             const int m = t / nrndm, n = t - m * nrndm;
@@ -528,7 +590,7 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
     __syncthreads();
     for (int size = 2; size <= npad; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < npad / 2; t += blockDim.x) {
+            for (int t = tid; t < npad / 2; t += nthr) {
                 const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
                 const bool up = ((lo & size) == 0);
                 const unsigned long long a = keys[lo], b = keys[hi];
@@ -547,7 +609,7 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
             const unsigned long long a = keys[t] >> 12, b = keys[t - 1] >> 12;
             return (a >> 4) != (b >> 4) || a == b;
         };
-        const int per = (npad + blockDim.x - 1) / blockDim.x;
+        const int per = (npad + nthr - 1) / nthr;
         const int t0 = tid * per, t1 = min(npairs, t0 + per);
         int cnt = 0;
         for (int t = t0; t < t1; ++t) cnt += head(t) ? 1 : 0;
@@ -566,10 +628,10 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
                 do { mask |= 1u << (unsigned)((keys[q] >> 12) & 15); ++q; } while (q < npairs && !head(q));
                 desc[rank++] = ((keys[t] >> 16) << 19) | ((unsigned long long)mask << 11) | (unsigned)t;
             }
-        if (tid == blockDim.x - 1) { s_U = base + incl; }
+        if (tid == nthr - 1) { s_U = base + incl; }
         __syncthreads();
     }
-    for (int t = tid; t < AS * npairs; t += blockDim.x) acc[t] = T(0);
+    for (int t = tid; t < AS * npairs; t += nthr) acc[t] = T(0);
     __syncthreads();
     const int U = s_U;
     const T K = xform_shift<T, TR, RULES>(psc);
@@ -809,13 +871,14 @@ __global__ __launch_bounds__(1024) void k_cdc_partial_grouped(const T *__restric
         s_sb[tid] = a; s_sbb[tid] = b; s_sb2[tid] = a2; s_sbb2[tid] = b2;
     }
     __syncthreads();
-    for (int p = tid; p < npairs; p += blockDim.x) {
+    for (int p = tid; p < npairs; p += nthr) {
         const unsigned long long key = keys[p];
         const int m = (int)((key >> 12) & 15), n = (int)(key & 4095);
         const double mA = (double)acc[AS * p], mAA = (double)acc[AS * p + 1];
         out[(int64_t)s_cells[m] * stride + n] = pearson_from_moments<T>(mA, mAA, (double)acc[AS * p + 2], s_sb[m], s_sbb[m], (double)G);
         if (DUAL) out2[(int64_t)s_cells[m] * stride + n] = pearson_from_moments<T>(mA, mAA, (double)acc[AS * p + 3], s_sb2[m], s_sbb2[m], (double)G);
     }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -913,6 +976,26 @@ __global__ void k_scatter_rows(const T *__restrict__ vals, const int32_t *__rest
 }
 
 // ---------------------------------------------------------------------------------------------
+// The list heads of the grouped kernel's unit queue: eight counters per (device, stream), allocated at the first grouped launch on
+// that stream and kept for the life of the process.  Launches on one stream are ordered, so they can share the eight words (each
+// launch zeroes them in-stream first); launches on different streams may overlap (the sharded schedule) and get their own.
+static int queue_heads(hipStream_t st, unsigned **out)
+{
+    static std::mutex mutex;
+    static std::map<std::pair<int, hipStream_t>, unsigned *> heads;
+    int dev = 0;
+    VCY_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mutex);
+    unsigned *&p = heads[std::make_pair(dev, st)];
+    if (!p) {
+        void *mem = nullptr;
+        VCY_CHECK_HIP(hipMalloc(&mem, 256));
+        p = static_cast<unsigned *>(mem);
+    }
+    *out = p;
+    return VCY_OK;
+}
+
 template <typename T, int TR, int RULES, int GC, int NV, bool DUAL>
 static int launch_grouped(const void *e, const void *d, const void *d2, const int32_t *ixs, void *out, void *out2, const int32_t *order, int64_t G,
                           int64_t ld, int64_t cell0, int64_t C_out, int64_t d_row0, int64_t nrndm, double psc, hipStream_t st,
@@ -972,10 +1055,18 @@ static int launch_grouped(const void *e, const void *d, const void *d2, const in
         }
         tw = (tile + bs - 1) / bs;
     }
+    // units of the queue: what used to be the blocks of the launch, in their order (a multiple of 8: one list per XCD); one persistent
+    // workgroup per CU draws them.  The eight list heads are zeroed in-stream: no host synchronisation, no allocation per call.
     auto nblocks = [&](int64_t ncell, int64_t w) { return ncell > 0 ? ((ncell + GC - 1) / GC + 7) / 8 * 8 * ((nrndm + w - 1) / w) : (int64_t)0; };
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks(c_main, tile) + nblocks(c_tail, tw))), dim3(1024), lds_g, st, (const T *)e, (const T *)d,
-                       (const T *)d2, ixs, (T *)out, (T *)out2, order, (int)G, ld, cell0, d_row0, (int)c_main, (int)tile, (int)c_tail, (int)tw,
-                       (int)nrndm, (int)nrndm, npad, (T)psc, fuse);
+    const int64_t nunits = nblocks(c_main, tile) + nblocks(c_tail, tw);
+    if (nunits > 0x7fffffff) return VCY_OK;
+    unsigned *queue = nullptr;
+    rc = queue_heads(st, &queue);
+    if (rc) return rc;
+    VCY_CHECK_HIP(hipMemsetAsync(queue, 0, 8 * sizeof(unsigned), st));
+    GroupedArgs<T> ga{(const T *)e, (const T *)d, (const T *)d2, ixs, (T *)out, (T *)out2, order, queue, ld, cell0, d_row0, (int)G, (int)c_main, (int)tile,
+                      (int)c_tail, (int)tw, (int)nrndm, (int)nrndm, npad, (int)nunits, (T)psc, fuse};
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nunits < W ? nunits : W)), dim3(1024), lds_g, st, ga);
     VCY_LAUNCH_CHECK();
     *done = true;
     return VCY_OK;
