@@ -23,6 +23,17 @@ def test_tsne_entry_points_refuse_null_pointers(L):
     assert b"null pointer" in L.vcy_last_error()
     assert L.vcy_tsne_workspace_bytes(1000, 2) > 0
     assert L.vcy_tsne_workspace_bytes(1000, 4) == 0 and L.vcy_tsne_workspace_bytes(1, 2) == 0
+    # both trees: N = 10, n_components = 2, angle 0.5; the parameters are (depth,) = (2,) and (leaf_size, max_depth) = (8, 24)
+    for tree, par in (("tree", (2,)), ("atree", (8, 24))):
+        calls = {"keys": (3, (10, *par)),
+                 "repulsion": (7, (10, *par, 0.5)),
+                 "gradient": (9, (10, 2, *par, 0.5, 1)),
+                 "step": (11, (10, 2, *par, 0.5, 0.5, 50.0, 0.01, 1))}
+        for what, (n_pointers, rest) in calls.items():
+            assert getattr(L, f"vcy_tsne_{tree}_{what}")(*[None] * n_pointers, *rest, None) == -1, (tree, what)
+            assert b"null pointer" in L.vcy_last_error(), (tree, what)
+    assert L.vcy_tsne_tree_workspace_bytes(10, 2) > 0
+    assert L.vcy_tsne_atree_workspace_bytes(10, 8, 24) > 0
 
 
 @pytest.mark.parametrize("kw,n,exc,msg", [

@@ -15,8 +15,12 @@
 //                        rows of P (+ the error terms), the gradient, and with STEP the gains / momentum / position update;
 //                        per-workgroup partials of the error and of |grad|^2.
 //   k_tsne_stats         KL and |grad|^2 from the partials (one workgroup), at the iterations whose error is asked for.
-//   k_tree_*, k_tsne_tree_repulsion  (vcy_tsne_tree_*, D = 2, opt-in) the repulsion by scikit-learn's Barnes-Hut acceptance rule with the
-//                        caller's angle on a complete quadtree; it fills the same partials, so k_tsne_step / k_tsne_stats are shared.
+//   k_tree_*, k_tsne_tree_repulsion    (vcy_tsne_tree_*, D = 2, opt-in) the repulsion by scikit-learn's Barnes-Hut acceptance rule with the
+//                        caller's angle on a complete quadtree of fixed depth;
+//   k_atree_*, k_tsne_atree_repulsion  (vcy_tsne_atree_*, D = 2, opt-in) the same rule on a quadtree as deep as the points are dense.
+// All three fill the same partials, so one tail serves them (tsne_tail: k_tsne_step, k_tsne_stats).  The trees own their build and the
+// control flow of their walk, and share: the frame of their keys (TreeFrame, tree_frame, tree_fill_w2), the walk's sums, acceptance, leaf sum
+// and stores (TreeAcc, tree_accept, tree_leaf_sweep, tree_walk_store), and on the host TreeTail, tree_check_shared, tree_eval, tree_rep_out.
 #include "common.h"
 #include <float.h>
 
@@ -277,39 +281,63 @@ static TsnePlan tsne_plan(int64_t N, int D)
     return p;
 }
 
-template <int D>
-static int tsne_launch(const float *Y, float *Yout, const int64_t *indptr, const int32_t *indices, const float *pval, float *grad,
-                       double *update, float *gains, double *stats, void *workspace, int64_t N, int compute_error, double momentum,
-                       double lr, double min_gain, bool step, hipStream_t s)
+// What a gradient (step false: grad is written) or an iteration (step true: Yout, update, gains) is asked for, whichever repulsion it uses.
+struct TsneArgs {
+    const float *Y;
+    float *Yout;
+    const int64_t *indptr; const int32_t *indices; const float *pval;      // P as CSR
+    float *grad;
+    double *update; float *gains;
+    double *stats;
+    int compute_error;
+    double momentum, lr, min_gain;
+    bool step;
+};
+
+// null pointers and aliasing, before anything else is looked at; `rest`: the entry point's other pointers are all there
+static int tsne_args_check(const TsneArgs &a, bool rest, const char *who)
 {
-    const TsnePlan p = tsne_plan(N, D);
-    char *w = (char *)workspace;
-    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off), *blk = (double *)(w + p.blk_off);
-    const int n = (int)N, nz = p.S * p.tb;
-    hipLaunchKernelGGL(k_tsne_repulsion<D>, dim3(p.tb, p.S), dim3(TSNE_TPB), 0, s, Y, part, zpart, n, p.per);
+    const bool out = a.step ? a.Yout && a.update && a.gains : a.grad != nullptr;
+    if (!(a.Y && a.indptr && a.indices && a.pval && a.stats && out && rest)) return fail(VCY_ERR_INVALID, "%s: null pointer", who);
+    if (a.step && a.Y == a.Yout) return fail(VCY_ERR_INVALID, "%s: Y_out must not alias Y (the attraction reads every row's old position)", who);
+    return VCY_OK;
+}
+
+// the tail of every evaluation, on the repulsion's partials (S splits of part, nz entries of zpart)
+template <int D>
+static int tsne_tail(const TsneArgs &a, const double *part, const double *zpart, int nz, int S, double *blk, int nb, int N, hipStream_t s)
+{
+    const auto step = a.step ? k_tsne_step<D, true> : k_tsne_step<D, false>;
+    hipLaunchKernelGGL(step, dim3(nb), dim3(TSNE_TPB), 0, s, a.Y, a.Yout, a.indptr, a.indices, a.pval, part, zpart, nz, S, a.grad, a.update,
+                       a.gains, blk, a.stats, N, a.compute_error, a.momentum, a.lr, (float)a.min_gain);
     VCY_LAUNCH_CHECK();
-    if (step)
-        hipLaunchKernelGGL((k_tsne_step<D, true>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, nz, p.S,
-                           grad, update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
-    else
-        hipLaunchKernelGGL((k_tsne_step<D, false>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, nz, p.S,
-                           grad, update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
-    VCY_LAUNCH_CHECK();
-    if (compute_error) {
-        hipLaunchKernelGGL(k_tsne_stats, dim3(1), dim3(TSNE_TPB), 0, s, blk, p.nb, stats);
+    if (a.compute_error) {
+        hipLaunchKernelGGL(k_tsne_stats, dim3(1), dim3(TSNE_TPB), 0, s, blk, nb, a.stats);
         VCY_LAUNCH_CHECK();
     }
     return VCY_OK;
 }
 
-static int tsne_dispatch(const float *Y, float *Yout, const int64_t *indptr, const int32_t *indices, const float *pval, float *grad,
-                         double *update, float *gains, double *stats, void *workspace, int64_t N, int D, int compute_error,
-                         double momentum, double lr, double min_gain, bool step, hipStream_t s)
+template <int D> static int tsne_launch(const TsneArgs &a, void *workspace, int64_t N, hipStream_t s)
 {
+    const TsnePlan p = tsne_plan(N, D);
+    char *w = (char *)workspace;
+    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off), *blk = (double *)(w + p.blk_off);
+    hipLaunchKernelGGL(k_tsne_repulsion<D>, dim3(p.tb, p.S), dim3(TSNE_TPB), 0, s, a.Y, part, zpart, (int)N, p.per);
+    VCY_LAUNCH_CHECK();
+    return tsne_tail<D>(a, part, zpart, p.S * p.tb, p.S, blk, p.nb, (int)N, s);
+}
+
+static int tsne_entry(const TsneArgs &a, void *workspace, int64_t N, int D, const char *who, hipStream_t s)
+{
+    const int rc = tsne_args_check(a, workspace != nullptr, who);
+    if (rc != VCY_OK) return rc;
+    if (!(N >= 2 && N < (1ll << 30))) return fail(VCY_ERR_INVALID, "%s: N out of range", who);
     switch (D) {
-    case 1: return tsne_launch<1>(Y, Yout, indptr, indices, pval, grad, update, gains, stats, workspace, N, compute_error, momentum, lr, min_gain, step, s);
-    case 2: return tsne_launch<2>(Y, Yout, indptr, indices, pval, grad, update, gains, stats, workspace, N, compute_error, momentum, lr, min_gain, step, s);
-    default: return tsne_launch<3>(Y, Yout, indptr, indices, pval, grad, update, gains, stats, workspace, N, compute_error, momentum, lr, min_gain, step, s);
+    case 1: return tsne_launch<1>(a, workspace, N, s);
+    case 2: return tsne_launch<2>(a, workspace, N, s);
+    case 3: return tsne_launch<3>(a, workspace, N, s);
+    default: return fail(VCY_ERR_INVALID, "%s: n_components must be 1, 2 or 3", who);
     }
 }
 
@@ -330,35 +358,53 @@ constexpr int TREE_MAX_DEPTH = 11;
 constexpr int TREE_BOX_BLOCKS = 256;               // workgroups of the min / max pass
 constexpr int TREE_RUN = 256;                      // f32 terms added between two f64 carries (as TSNE_TILE in the exact kernel)
 
-struct TreeHead {
+struct TreeFrame {                                 // the frame either tree's keys are taken in
     double lo[2], side, scale;                     // box corner, larger extent, 2^depth / side (0 when side is 0 or not finite)
+};
+struct TreeHead {
+    TreeFrame fr;
     float w2[TREE_MAX_DEPTH + 1];                  // f32((side 2^-l)^2)
     float pad[12];
 };
 static_assert(sizeof(TreeHead) == 128, "TreeHead");
 
-struct TreePlan {
-    int L, nbx, tb, nb;
-    int64_t cells, nodes;
-    size_t boxp_off, node_off, start_off, ysort_off, part_off, zpart_off, blk_off, bytes;
-};
 static size_t tree_align(size_t b) { return (b + 127) / 128 * 128; }
+
+// What the workspace of either tree ends in, from the first byte after the tree's own regions: sorted positions | part (3, N) f64 |
+// zpart | blk, and the grids that go with them (nbx: workgroups of the box pass, tb: of the walk = entries of zpart, nb: of k_tsne_step).
+struct TreeTail {
+    int nbx, tb, nb;
+    size_t ysort_off, part_off, zpart_off, blk_off, bytes;
+};
+static TreeTail tree_tail(int64_t N, size_t first)
+{
+    TreeTail t;
+    t.tb = t.nb = (int)((N + TSNE_TPB - 1) / TSNE_TPB);
+    t.nbx = t.nb < TREE_BOX_BLOCKS ? t.nb : TREE_BOX_BLOCKS;
+    t.ysort_off = first;
+    t.part_off = t.ysort_off + tree_align(sizeof(float2) * (size_t)N);
+    t.zpart_off = t.part_off + tree_align(sizeof(double) * 3 * (size_t)N);
+    t.blk_off = t.zpart_off + tree_align(sizeof(double) * (size_t)t.tb);
+    t.bytes = t.blk_off + tree_align(sizeof(double) * 2 * (size_t)t.nb);
+    return t;
+}
+
+struct TreePlan {
+    int L;
+    int64_t cells, nodes;
+    size_t boxp_off, node_off, start_off;
+    TreeTail t;
+};
 static TreePlan tree_plan(int64_t N, int L)
 {
     TreePlan p;
     p.L = L;
     p.cells = 1ll << (2 * L);
     p.nodes = ((1ll << (2 * L + 2)) - 1) / 3;
-    p.nbx = (int)((N + TSNE_TPB - 1) / TSNE_TPB < TREE_BOX_BLOCKS ? (N + TSNE_TPB - 1) / TSNE_TPB : TREE_BOX_BLOCKS);
-    p.tb = p.nb = (int)((N + TSNE_TPB - 1) / TSNE_TPB);
     p.boxp_off = sizeof(TreeHead);
     p.node_off = p.boxp_off + tree_align(sizeof(float4) * TREE_BOX_BLOCKS);
     p.start_off = p.node_off + tree_align(16 * (size_t)p.nodes);
-    p.ysort_off = p.start_off + tree_align(sizeof(int) * (size_t)(p.cells + 1));
-    p.part_off = p.ysort_off + tree_align(sizeof(float2) * (size_t)N);
-    p.zpart_off = p.part_off + tree_align(sizeof(double) * 3 * (size_t)N);
-    p.blk_off = p.zpart_off + tree_align(sizeof(double) * (size_t)p.tb);
-    p.bytes = p.blk_off + tree_align(sizeof(double) * 2 * (size_t)p.nb);
+    p.t = tree_tail(N, p.start_off + tree_align(sizeof(int) * (size_t)(p.cells + 1)));
     return p;
 }
 
@@ -419,27 +465,41 @@ __device__ __forceinline__ unsigned tree_cell(float y, double lo, double scale, 
     return t >= top ? (unsigned)((1 << L) - 1) : (unsigned)(int)floor(t);
 }
 
+// the frame of `bits` key bits per axis from the box partials: every workgroup reduces them to the same box
+__device__ __forceinline__ TreeFrame tree_frame(const float4 *__restrict__ boxp, int nbx, int bits, float4 *s_box)
+{
+    float4 b = (int)threadIdx.x < nbx ? boxp[threadIdx.x] : make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
+    b = tree_block_box(b, s_box);
+    TreeFrame f;
+    f.lo[0] = (double)b.x; f.lo[1] = (double)b.y;
+    f.side = fmax(__dsub_rn((double)b.z, f.lo[0]), __dsub_rn((double)b.w, f.lo[1]));
+    f.scale = (f.side > 0.0 && f.side < INFINITY) ? __ddiv_rn((double)(1 << bits), f.side) : 0.0;
+    return f;
+}
+
+// w2[l] = f32((side 2^-l)^2), l = 0 .. levels
+__device__ __forceinline__ void tree_fill_w2(float *__restrict__ w2, double side, int levels)
+{
+    for (int l = 0; l <= levels; ++l) {
+        const double s = __dmul_rn(side, 1.0 / (double)(1 << l));
+        w2[l] = (float)__dmul_rn(s, s);
+    }
+}
+
 __global__ __launch_bounds__(TSNE_TPB) void k_tree_keys(const float2 *__restrict__ Y, const float4 *__restrict__ boxp, int nbx,
                                                         TreeHead *__restrict__ head, int32_t *__restrict__ keys, int N, int L)
 {
     __shared__ float4 s_box[TSNE_TPB / VCY_WAVE];
-    float4 b = (int)threadIdx.x < nbx ? boxp[threadIdx.x] : make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
-    b = tree_block_box(b, s_box);                                      // every workgroup: the same box
-    const double lox = (double)b.x, loy = (double)b.y;
-    const double side = fmax(__dsub_rn((double)b.z, lox), __dsub_rn((double)b.w, loy));
-    const double scale = (side > 0.0 && side < INFINITY) ? __ddiv_rn((double)(1 << L), side) : 0.0;
+    const TreeFrame f = tree_frame(boxp, nbx, L, s_box);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        head->lo[0] = lox; head->lo[1] = loy; head->side = side; head->scale = scale;
-        for (int l = 0; l <= TREE_MAX_DEPTH; ++l) {
-            const double s = __dmul_rn(side, 1.0 / (double)(1 << l));
-            head->w2[l] = (float)__dmul_rn(s, s);
-        }
+        head->fr = f;
+        tree_fill_w2(head->w2, f.side, TREE_MAX_DEPTH);
         for (int l = 0; l < 12; ++l) head->pad[l] = 0.0f;
     }
     const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
     if (i < N) {
         const float2 y = Y[i];
-        keys[i] = (int32_t)(tree_spread(tree_cell(y.x, lox, scale, L)) | (tree_spread(tree_cell(y.y, loy, scale, L)) << 1));
+        keys[i] = (int32_t)(tree_spread(tree_cell(y.x, f.lo[0], f.scale, L)) | (tree_spread(tree_cell(y.y, f.lo[1], f.scale, L)) << 1));
     }
 }
 
@@ -519,6 +579,72 @@ __global__ __launch_bounds__(TSNE_TPB) void k_tree_finalize(void *nodes, const i
     ((int4 *)nodes)[idx] = r;
 }
 
+// What the walks of both trees share.  A lane's sums: f32 of at most TREE_RUN terms (run counts them), carried into f64; the visit counts
+struct TreeAcc {
+    double F[2] = {0.0, 0.0}, W = 0.0;
+    float f[2] = {0.0f, 0.0f}, w = 0.0f;
+    int run = 0, n_acc = 0, n_dir = 0;
+    __device__ __forceinline__ void carry()
+    {
+        F[0] += (double)f[0]; F[1] += (double)f[1]; W += (double)w;
+        f[0] = f[1] = w = 0.0f;
+        run = 0;
+    }
+};
+
+// scikit-learn's rule for target t and a node of cnt points around (cx, cy) of squared width *w2 (read by active lanes only): the lane
+// takes the node when *w2 < th2 d^2 (separately rounded), and then adds the pair arithmetic of tsne_pair<2> with a multiplicity
+__device__ __forceinline__ bool tree_accept(TreeAcc &a, const float (&t)[2], float cx, float cy, int cnt, const float *w2, float th2, bool active)
+{
+    const float dx = __fsub_rn(t[0], cx), dy = __fsub_rn(t[1], cy);
+    const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+    const bool take = active && *w2 < __fmul_rn(th2, d2);
+    if (take) {
+        const float q = __builtin_amdgcn_rcpf(fmaf(dy, dy, fmaf(dx, dx, 1.0f)));
+        const float cq = (float)cnt * q, cq2 = cq * q;
+        a.f[0] = fmaf(cq2, dx, a.f[0]);
+        a.f[1] = fmaf(cq2, dy, a.f[1]);
+        a.w += cq;
+        ++a.n_acc;
+    }
+    return take;
+}
+
+// The points [b, e) of the sorted order one by one, for the lanes with `open` (p: the lane's own position, left out): 64 points per
+// load, one per lane (every lane of the wave is here: the caller's branch is uniform), then broadcast one by one.
+__device__ __forceinline__ void tree_leaf_sweep(TreeAcc &a, const float (&t)[2], const float2 *__restrict__ ysort, int b, int e, int p, bool open)
+{
+    for (int c0 = b; c0 < e; c0 += VCY_WAVE) {
+        const int n = min(e - c0, VCY_WAVE), mine = c0 + (int)(threadIdx.x & 63);
+        if (a.run + n > TREE_RUN) a.carry();
+        const float2 sp = mine < e ? ysort[mine] : make_float2(0.0f, 0.0f);
+        for (int u = 0; u < n; ++u) {
+            const float s[2] = {readlane_t(sp.x, u), readlane_t(sp.y, u)};
+            if (open && c0 + u != p) tsne_pair<2>(t, s, a.f, a.w);
+        }
+        a.run += n;
+    }
+    if (open && e > b) a.n_dir += (e - b) - (p >= b && p < e ? 1 : 0);
+}
+
+// the last carry, then the lane's sums at its point's own index (part), its visit counts, and the workgroup's share of Z (zpart)
+template <bool VISITS>
+__device__ __forceinline__ void tree_walk_store(TreeAcc &a, bool valid, int p, const int64_t *__restrict__ order, double *__restrict__ part,
+                                                double *__restrict__ zpart, int32_t *__restrict__ visits, int N, double *s_red)
+{
+    a.carry();
+    if (valid) {
+        const int64_t o64 = order[p];
+        const size_t o = (uint64_t)o64 < (uint64_t)N ? (size_t)o64 : 0;
+        part[o] = a.F[0];
+        part[(size_t)N + o] = a.F[1];
+        part[2 * (size_t)N + o] = a.W;
+        if constexpr (VISITS) { visits[2 * o] = a.n_acc; visits[2 * o + 1] = a.n_dir; }
+    }
+    const double zsum = block_sum(valid ? a.W : 0.0, s_red);
+    if (threadIdx.x == 0) zpart[blockIdx.x] = zsum;
+}
+
 // One wave per 64 consecutive targets of the sorted order.  (l, m) is wave-uniform and moves in depth-first order: down to
 // (l + 1, 4 m) while any lane wants to open, else on to the next sibling, climbing while m & 3 == 3.  acc is the level at
 // which the lane accepted an ancestor of the current node (64: none, -1: no target): the lane sits out until the walk is back
@@ -536,17 +662,10 @@ __global__ __launch_bounds__(TSNE_TPB) void k_tsne_tree_repulsion(const int4 *__
     const float2 tp = valid ? ysort[p] : make_float2(0.0f, 0.0f);
     const float t[2] = {tp.x, tp.y};
     int acc = valid ? 64 : -1;
-    double F[2] = {0.0, 0.0}, W = 0.0;
-    float f[2] = {0.0f, 0.0f}, w = 0.0f;
-    int run = 0, n_acc = 0, n_dir = 0;
+    TreeAcc a;
     const unsigned nn = tree_level_offset(L + 1);
     int l = 0;
     unsigned m = 0;
-    auto carry = [&]() {
-        F[0] += (double)f[0]; F[1] += (double)f[1]; W += (double)w;
-        f[0] = f[1] = w = 0.0f;
-        run = 0;
-    };
     for (unsigned trip = 0; trip < nn; ++trip) {
         const int4 nd = node[tree_level_offset(l) + m];
         const int cnt = __builtin_amdgcn_readfirstlane(nd.x);
@@ -554,39 +673,17 @@ __global__ __launch_bounds__(TSNE_TPB) void k_tsne_tree_repulsion(const int4 *__
         if (cnt > 0) {
             if (acc >= l) acc = 64;
             const bool active = acc == 64;
-            if (run + 1 > TREE_RUN) carry();
-            const float cx = __int_as_float(nd.y), cy = __int_as_float(nd.z);
-            const float dx = __fsub_rn(t[0], cx), dy = __fsub_rn(t[1], cy);
-            const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-            const bool take = active && head->w2[l] < __fmul_rn(th2, d2);
-            if (take) {                                                // the pair arithmetic of tsne_pair<2> with a multiplicity
-                const float q = __builtin_amdgcn_rcpf(fmaf(dy, dy, fmaf(dx, dx, 1.0f)));
-                const float cq = (float)cnt * q, cq2 = cq * q;
-                f[0] = fmaf(cq2, dx, f[0]);
-                f[1] = fmaf(cq2, dy, f[1]);
-                w += cq;
-                acc = l;
-                ++n_acc;
-            }
-            ++run;
+            if (a.run + 1 > TREE_RUN) a.carry();
+            const bool take = tree_accept(a, t, __int_as_float(nd.y), __int_as_float(nd.z), cnt, head->w2 + l, th2, active);
+            if (take) acc = l;
+            ++a.run;
             const bool open = active && !take;
             const bool any_open = __ballot(open) != 0ull;
             if (l < L) {
                 descend = any_open;
             } else if (any_open) {                                     // a leaf somebody does not accept: its points one by one
-                // 64 points per load, one per lane (every lane of the wave is here: the branch is uniform), then broadcast one by one
                 const int b = max(__builtin_amdgcn_readfirstlane(start[m]), 0), e = min(__builtin_amdgcn_readfirstlane(start[m + 1]), N);
-                for (int c0 = b; c0 < e; c0 += VCY_WAVE) {
-                    const int n = min(e - c0, VCY_WAVE), mine = c0 + (int)(threadIdx.x & 63);
-                    if (run + n > TREE_RUN) carry();
-                    const float2 sp = mine < e ? ysort[mine] : make_float2(0.0f, 0.0f);
-                    for (int u = 0; u < n; ++u) {
-                        const float s[2] = {readlane_t(sp.x, u), readlane_t(sp.y, u)};
-                        if (open && c0 + u != p) tsne_pair<2>(t, s, f, w);
-                    }
-                    run += n;
-                }
-                if (open && e > b) n_dir += (e - b) - (p >= b && p < e ? 1 : 0);
+                tree_leaf_sweep(a, t, ysort, b, e, p, open);
             }
         }
         if (descend) {
@@ -598,17 +695,7 @@ __global__ __launch_bounds__(TSNE_TPB) void k_tsne_tree_repulsion(const int4 *__
             ++m;
         }
     }
-    carry();
-    if (valid) {
-        const int64_t o64 = order[p];
-        const size_t o = (uint64_t)o64 < (uint64_t)N ? (size_t)o64 : 0;
-        part[o] = F[0];
-        part[(size_t)N + o] = F[1];
-        part[2 * (size_t)N + o] = W;
-        if constexpr (VISITS) { visits[2 * o] = n_acc; visits[2 * o + 1] = n_dir; }
-    }
-    const double zsum = block_sum(valid ? W : 0.0, s_red);
-    if (threadIdx.x == 0) zpart[blockIdx.x] = zsum;
+    tree_walk_store<VISITS>(a, valid, p, order, part, zpart, visits, N, s_red);
 }
 
 // rep (N, 3) = force x, y and W of every point from part (3, N); Z = the sum of zpart in k_tsne_step's order
@@ -625,6 +712,25 @@ __global__ __launch_bounds__(TSNE_TPB) void k_tree_rep_out(const double *__restr
         for (int a = 0; a < 3; ++a) rep[(size_t)i * 3 + a] = part[(size_t)a * N + i];
 }
 
+// what both trees are refused for alike; each adds the checks of its own parameters
+static int tree_check_shared(int64_t N, int n_components, double angle, const char *who)
+{
+    if (n_components != 2) return fail(VCY_ERR_UNSUPPORTED, "%s: the tree repulsion covers n_components == 2 only", who);
+    if (!(N >= 2 && N < (1ll << 30))) return fail(VCY_ERR_INVALID, "%s: N out of range", who);
+    if (!(angle >= 0.0 && angle <= 1.0)) return fail(VCY_ERR_INVALID, "%s: angle must be in [0, 1]", who);
+    return VCY_OK;
+}
+
+// the end of either tree's _repulsion entry point: rep and Z from the partials its walk left in the workspace
+static int tree_rep_out(const TreeTail &t, void *workspace, double *rep, double *Z, int64_t N, hipStream_t s)
+{
+    const char *w = (const char *)workspace;
+    hipLaunchKernelGGL(k_tree_rep_out, dim3(t.nb), dim3(TSNE_TPB), 0, s, (const double *)(w + t.part_off), (const double *)(w + t.zpart_off), t.tb,
+                       rep, Z, (int)N);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
 // build + traversal: part, zpart of the workspace are what k_tsne_step<2, .> reads with one split
 static int tree_repulsion_launch(const float *Y, const int64_t *order, const int32_t *skeys, int32_t *visits, void *workspace, const TreePlan &p,
                                  int64_t N, double angle, hipStream_t s)
@@ -632,64 +738,33 @@ static int tree_repulsion_launch(const float *Y, const int64_t *order, const int
     char *w = (char *)workspace;
     const int n = (int)N, L = p.L;
     int *start = (int *)(w + p.start_off);
-    float2 *ysort = (float2 *)(w + p.ysort_off);
+    float2 *ysort = (float2 *)(w + p.t.ysort_off);
     void *nodes = w + p.node_off;
     hipLaunchKernelGGL(k_tree_start, dim3((unsigned)((p.cells + 1 + TSNE_TPB - 1) / TSNE_TPB)), dim3(TSNE_TPB), 0, s, skeys, start, n, (unsigned)p.cells);
     VCY_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tree_gather, dim3(p.nb), dim3(TSNE_TPB), 0, s, (const float2 *)Y, order, ysort, n);
+    hipLaunchKernelGGL(k_tree_gather, dim3(p.t.nb), dim3(TSNE_TPB), 0, s, (const float2 *)Y, order, ysort, n);
     VCY_LAUNCH_CHECK();
     for (int l0 = L; l0 >= 0; l0 -= 5) {
         const unsigned g = (unsigned)(((1ll << (2 * l0)) + TSNE_TPB - 1) / TSNE_TPB);
-        if (l0 == L)
-            hipLaunchKernelGGL(k_tree_up<true>, dim3(g), dim3(TSNE_TPB), 0, s, (double2 *)nodes, start, ysort, n, l0);
-        else
-            hipLaunchKernelGGL(k_tree_up<false>, dim3(g), dim3(TSNE_TPB), 0, s, (double2 *)nodes, start, ysort, n, l0);
+        const auto up = l0 == L ? k_tree_up<true> : k_tree_up<false>;
+        hipLaunchKernelGGL(up, dim3(g), dim3(TSNE_TPB), 0, s, (double2 *)nodes, start, ysort, n, l0);
         VCY_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_tree_finalize, dim3((unsigned)((p.nodes + TSNE_TPB - 1) / TSNE_TPB)), dim3(TSNE_TPB), 0, s, nodes, start, L, (unsigned)p.nodes);
     VCY_LAUNCH_CHECK();
     const float th2 = (float)(angle * angle);
-    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off);
-    if (visits)
-        hipLaunchKernelGGL(k_tsne_tree_repulsion<true>, dim3(p.tb), dim3(TSNE_TPB), 0, s, (const int4 *)nodes, start, ysort, order,
-                           (const TreeHead *)w, part, zpart, visits, n, L, th2);
-    else
-        hipLaunchKernelGGL(k_tsne_tree_repulsion<false>, dim3(p.tb), dim3(TSNE_TPB), 0, s, (const int4 *)nodes, start, ysort, order,
-                           (const TreeHead *)w, part, zpart, visits, n, L, th2);
+    double *part = (double *)(w + p.t.part_off), *zpart = (double *)(w + p.t.zpart_off);
+    const auto walk = visits ? k_tsne_tree_repulsion<true> : k_tsne_tree_repulsion<false>;
+    hipLaunchKernelGGL(walk, dim3(p.t.tb), dim3(TSNE_TPB), 0, s, (const int4 *)nodes, start, ysort, order, (const TreeHead *)w, part, zpart, visits, n, L, th2);
     VCY_LAUNCH_CHECK();
-    return VCY_OK;
-}
-
-static int tree_launch(const float *Y, float *Yout, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
-                       const int32_t *skeys, float *grad, double *update, float *gains, double *stats, void *workspace, int64_t N, int depth,
-                       double angle, int compute_error, double momentum, double lr, double min_gain, bool step, hipStream_t s)
-{
-    const TreePlan p = tree_plan(N, depth);
-    const int rc = tree_repulsion_launch(Y, order, skeys, nullptr, workspace, p, N, angle, s);
-    if (rc != VCY_OK) return rc;
-    char *w = (char *)workspace;
-    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off), *blk = (double *)(w + p.blk_off);
-    const int n = (int)N;
-    if (step)
-        hipLaunchKernelGGL((k_tsne_step<2, true>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
-                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
-    else
-        hipLaunchKernelGGL((k_tsne_step<2, false>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
-                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
-    VCY_LAUNCH_CHECK();
-    if (compute_error) {
-        hipLaunchKernelGGL(k_tsne_stats, dim3(1), dim3(TSNE_TPB), 0, s, blk, p.nb, stats);
-        VCY_LAUNCH_CHECK();
-    }
     return VCY_OK;
 }
 
 static int tree_check(int64_t N, int n_components, int depth, double angle, const char *who)
 {
-    if (n_components != 2) return fail(VCY_ERR_UNSUPPORTED, "%s: the tree repulsion covers n_components == 2 only", who);
-    if (!(N >= 2 && N < (1ll << 30))) return fail(VCY_ERR_INVALID, "%s: N out of range", who);
+    const int rc = tree_check_shared(N, n_components, angle, who);
+    if (rc != VCY_OK) return rc;
     if (depth < 1 || depth > TREE_MAX_DEPTH) return fail(VCY_ERR_INVALID, "%s: depth must be 1 .. 11", who);
-    if (!(angle >= 0.0 && angle <= 1.0)) return fail(VCY_ERR_INVALID, "%s: angle must be in [0, 1]", who);
     return VCY_OK;
 }
 
@@ -716,7 +791,7 @@ constexpr int ATREE_SCAN_CHUNK = TSNE_TPB * ATREE_SCAN_ITEMS;
 constexpr int ATREE_GRID = 2048;                                       // workgroups of the kernels that loop over the nodes (their number is on the device)
 
 struct ATreeHead {
-    double lo[2], side, scale;                     // box corner, larger extent, 2^depth / side (0 when side is 0 or not finite)
+    TreeFrame fr;
     float w2[ATREE_MAX_DEPTH + 1];                 // f32((side 2^-l)^2)
     int n_nodes;                                   // nodes of this evaluation (<= cap)
     int depth, leaf_size;
@@ -732,9 +807,10 @@ struct ATreeNode {                                 // 32 bytes: one scalar load
 static_assert(sizeof(ATreeNode) == 32, "ATreeNode");
 
 struct ATreePlan {
-    int D, leaf, nbx, tb, nb, nchunk;
+    int D, leaf, nchunk;
     int64_t cap;
-    size_t boxp_off, node_off, nsum_off, flag_off, scan_off, chunk_off, ysort_off, part_off, zpart_off, blk_off, bytes;
+    size_t boxp_off, node_off, nsum_off, flag_off, scan_off, chunk_off;
+    TreeTail t;
 };
 static int64_t atree_cap(int64_t N, int leaf, int D) { return 1 + 4 * (int64_t)D * (N / ((int64_t)leaf + 1)); }
 static ATreePlan atree_plan(int64_t N, int leaf, int D)
@@ -743,8 +819,6 @@ static ATreePlan atree_plan(int64_t N, int leaf, int D)
     p.D = D;
     p.leaf = leaf;
     p.cap = atree_cap(N, leaf, D);
-    p.nbx = (int)((N + TSNE_TPB - 1) / TSNE_TPB < TREE_BOX_BLOCKS ? (N + TSNE_TPB - 1) / TSNE_TPB : TREE_BOX_BLOCKS);
-    p.tb = p.nb = (int)((N + TSNE_TPB - 1) / TSNE_TPB);
     p.nchunk = (int)((N + ATREE_SCAN_CHUNK - 1) / ATREE_SCAN_CHUNK);
     p.boxp_off = sizeof(ATreeHead);
     p.node_off = p.boxp_off + tree_align(sizeof(float4) * TREE_BOX_BLOCKS);
@@ -752,11 +826,7 @@ static ATreePlan atree_plan(int64_t N, int leaf, int D)
     p.flag_off = p.nsum_off + tree_align(sizeof(double2) * (size_t)p.cap);
     p.scan_off = p.flag_off + tree_align(sizeof(int) * (size_t)N);
     p.chunk_off = p.scan_off + tree_align(sizeof(int) * (size_t)(N + 1));
-    p.ysort_off = p.chunk_off + tree_align(sizeof(int) * (size_t)(p.nchunk + 1));
-    p.part_off = p.ysort_off + tree_align(sizeof(float2) * (size_t)N);
-    p.zpart_off = p.part_off + tree_align(sizeof(double) * 3 * (size_t)N);
-    p.blk_off = p.zpart_off + tree_align(sizeof(double) * (size_t)p.tb);
-    p.bytes = p.blk_off + tree_align(sizeof(double) * 2 * (size_t)p.nb);
+    p.t = tree_tail(N, p.chunk_off + tree_align(sizeof(int) * (size_t)(p.nchunk + 1)));
     return p;
 }
 
@@ -774,24 +844,17 @@ __global__ __launch_bounds__(TSNE_TPB) void k_atree_keys(const float2 *__restric
                                                          ATreeHead *__restrict__ head, int64_t *__restrict__ keys, int N, int D, int leaf)
 {
     __shared__ float4 s_box[TSNE_TPB / VCY_WAVE];
-    float4 b = (int)threadIdx.x < nbx ? boxp[threadIdx.x] : make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
-    b = tree_block_box(b, s_box);                                      // every workgroup: the same box
-    const double lox = (double)b.x, loy = (double)b.y;
-    const double side = fmax(__dsub_rn((double)b.z, lox), __dsub_rn((double)b.w, loy));
-    const double scale = (side > 0.0 && side < INFINITY) ? __ddiv_rn((double)(1 << D), side) : 0.0;
+    const TreeFrame f = tree_frame(boxp, nbx, D, s_box);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        head->lo[0] = lox; head->lo[1] = loy; head->side = side; head->scale = scale;
-        for (int l = 0; l <= ATREE_MAX_DEPTH; ++l) {
-            const double s = __dmul_rn(side, 1.0 / (double)(1 << l));
-            head->w2[l] = (float)__dmul_rn(s, s);
-        }
+        head->fr = f;
+        tree_fill_w2(head->w2, f.side, ATREE_MAX_DEPTH);
         head->n_nodes = 0; head->depth = D; head->leaf_size = leaf;
         for (int l = 0; l < 28; ++l) head->pad[l] = 0;
     }
     const int i = blockIdx.x * TSNE_TPB + threadIdx.x;
     if (i < N) {
         const float2 y = Y[i];
-        keys[i] = (int64_t)(atree_spread(tree_cell(y.x, lox, scale, D)) | (atree_spread(tree_cell(y.y, loy, scale, D)) << 1));
+        keys[i] = (int64_t)(atree_spread(tree_cell(y.x, f.lo[0], f.scale, D)) | (atree_spread(tree_cell(y.y, f.lo[1], f.scale, D)) << 1));
     }
 }
 
@@ -979,15 +1042,8 @@ __global__ __launch_bounds__(TSNE_TPB) void k_tsne_atree_repulsion(const ATreeNo
     const float2 tp = valid ? ysort[p] : make_float2(0.0f, 0.0f);
     const float t[2] = {tp.x, tp.y};
     int until = valid ? 0 : 0x7fffffff;
-    double F[2] = {0.0, 0.0}, W = 0.0;
-    float f[2] = {0.0f, 0.0f}, w = 0.0f;
-    int run = 0, n_acc = 0, n_dir = 0;
+    TreeAcc a;
     const int nn = __builtin_amdgcn_readfirstlane(head->n_nodes);
-    auto carry = [&]() {
-        F[0] += (double)f[0]; F[1] += (double)f[1]; W += (double)w;
-        f[0] = f[1] = w = 0.0f;
-        run = 0;
-    };
     int i = 0;
     for (int trip = 0; trip < nn && i < nn; ++trip) {
         i = __builtin_amdgcn_readfirstlane(i);
@@ -995,55 +1051,24 @@ __global__ __launch_bounds__(TSNE_TPB) void k_tsne_atree_repulsion(const ATreeNo
         const int cnt = __builtin_amdgcn_readfirstlane(nd.count), lvl = min(max(__builtin_amdgcn_readfirstlane(nd.level), 0), ATREE_MAX_DEPTH);
         const int skip = max(__builtin_amdgcn_readfirstlane(nd.skip), i + 1), leaf = __builtin_amdgcn_readfirstlane(nd.leaf);
         const bool active = i >= until;
-        if (run + 1 > TREE_RUN) carry();
-        const float dx = __fsub_rn(t[0], nd.cx), dy = __fsub_rn(t[1], nd.cy);
-        const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-        const bool take = active && head->w2[lvl] < __fmul_rn(th2, d2);
-        if (take) {                                                    // the pair arithmetic of tsne_pair<2> with a multiplicity
-            const float q = __builtin_amdgcn_rcpf(fmaf(dy, dy, fmaf(dx, dx, 1.0f)));
-            const float cq = (float)cnt * q, cq2 = cq * q;
-            f[0] = fmaf(cq2, dx, f[0]);
-            f[1] = fmaf(cq2, dy, f[1]);
-            w += cq;
-            until = skip;
-            ++n_acc;
-        }
-        ++run;
+        if (a.run + 1 > TREE_RUN) a.carry();
+        const bool take = tree_accept(a, t, nd.cx, nd.cy, cnt, head->w2 + lvl, th2, active);
+        if (take) until = skip;
+        ++a.run;
         const bool open = active && !take;
         const bool any_open = __ballot(open) != 0ull;
         if (leaf && any_open) {
-            // 64 points per load, one per lane (every lane of the wave is here: the branch is uniform), then broadcast one by one
             const int b = max(__builtin_amdgcn_readfirstlane(nd.start), 0), e = min(b + max(cnt, 0), N);
-            for (int c0 = b; c0 < e; c0 += VCY_WAVE) {
-                const int n = min(e - c0, VCY_WAVE), mine = c0 + (int)(threadIdx.x & 63);
-                if (run + n > TREE_RUN) carry();
-                const float2 sp = mine < e ? ysort[mine] : make_float2(0.0f, 0.0f);
-                for (int u = 0; u < n; ++u) {
-                    const float s[2] = {readlane_t(sp.x, u), readlane_t(sp.y, u)};
-                    if (open && c0 + u != p) tsne_pair<2>(t, s, f, w);
-                }
-                run += n;
-            }
-            if (open && e > b) n_dir += (e - b) - (p >= b && p < e ? 1 : 0);
+            tree_leaf_sweep(a, t, ysort, b, e, p, open);
         }
         i = (!leaf && any_open) ? i + 1 : skip;
     }
-    carry();
-    if (valid) {
-        const int64_t o64 = order[p];
-        const size_t o = (uint64_t)o64 < (uint64_t)N ? (size_t)o64 : 0;
-        part[o] = F[0];
-        part[(size_t)N + o] = F[1];
-        part[2 * (size_t)N + o] = W;
-        if constexpr (VISITS) { visits[2 * o] = n_acc; visits[2 * o + 1] = n_dir; }
-    }
-    const double zsum = block_sum(valid ? W : 0.0, s_red);
-    if (threadIdx.x == 0) zpart[blockIdx.x] = zsum;
+    tree_walk_store<VISITS>(a, valid, p, order, part, zpart, visits, N, s_red);
 }
 
 // build + traversal: part, zpart of the workspace are what k_tsne_step<2, .> reads with one split
-static int atree_repulsion_launch(const float *Y, const int64_t *order, const int64_t *skeys, int32_t *visits, void *workspace, const ATreePlan &p,
-                                  int64_t N, double angle, hipStream_t s)
+static int tree_repulsion_launch(const float *Y, const int64_t *order, const int64_t *skeys, int32_t *visits, void *workspace, const ATreePlan &p,
+                                 int64_t N, double angle, hipStream_t s)
 {
     char *w = (char *)workspace;
     const int n = (int)N, D = p.D;
@@ -1051,14 +1076,14 @@ static int atree_repulsion_launch(const float *Y, const int64_t *order, const in
     ATreeNode *node = (ATreeNode *)(w + p.node_off);
     double2 *nsum = (double2 *)(w + p.nsum_off);
     int *flag = (int *)(w + p.flag_off), *scan = (int *)(w + p.scan_off), *chunk = (int *)(w + p.chunk_off);
-    float2 *ysort = (float2 *)(w + p.ysort_off);
-    hipLaunchKernelGGL(k_atree_flag, dim3(p.nb), dim3(TSNE_TPB), 0, s, skeys, (const float2 *)Y, order, flag, ysort, n, D, p.leaf);
+    float2 *ysort = (float2 *)(w + p.t.ysort_off);
+    hipLaunchKernelGGL(k_atree_flag, dim3(p.t.nb), dim3(TSNE_TPB), 0, s, skeys, (const float2 *)Y, order, flag, ysort, n, D, p.leaf);
     VCY_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_atree_scan1, dim3(p.nchunk), dim3(TSNE_TPB), 0, s, flag, scan, chunk, n);
     VCY_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_atree_scan2, dim3(1), dim3(TSNE_TPB), 0, s, chunk, p.nchunk, head, scan, n, (long long)p.cap);
     VCY_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_atree_emit, dim3(p.nb), dim3(TSNE_TPB), 0, s, skeys, flag, scan, chunk, p.nchunk, node, n, D, p.leaf, (long long)p.cap);
+    hipLaunchKernelGGL(k_atree_emit, dim3(p.t.nb), dim3(TSNE_TPB), 0, s, skeys, flag, scan, chunk, p.nchunk, node, n, D, p.leaf, (long long)p.cap);
     VCY_LAUNCH_CHECK();
     const int64_t want = (p.cap + TSNE_TPB - 1) / TSNE_TPB;
     const unsigned g = (unsigned)(want < ATREE_GRID ? want : ATREE_GRID);
@@ -1067,36 +1092,10 @@ static int atree_repulsion_launch(const float *Y, const int64_t *order, const in
         VCY_LAUNCH_CHECK();
     }
     const float th2 = (float)(angle * angle);
-    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off);
-    if (visits)
-        hipLaunchKernelGGL(k_tsne_atree_repulsion<true>, dim3(p.tb), dim3(TSNE_TPB), 0, s, node, ysort, order, head, part, zpart, visits, n, th2);
-    else
-        hipLaunchKernelGGL(k_tsne_atree_repulsion<false>, dim3(p.tb), dim3(TSNE_TPB), 0, s, node, ysort, order, head, part, zpart, visits, n, th2);
+    double *part = (double *)(w + p.t.part_off), *zpart = (double *)(w + p.t.zpart_off);
+    const auto walk = visits ? k_tsne_atree_repulsion<true> : k_tsne_atree_repulsion<false>;
+    hipLaunchKernelGGL(walk, dim3(p.t.tb), dim3(TSNE_TPB), 0, s, node, ysort, order, head, part, zpart, visits, n, th2);
     VCY_LAUNCH_CHECK();
-    return VCY_OK;
-}
-
-static int atree_launch(const float *Y, float *Yout, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
-                        const int64_t *skeys, float *grad, double *update, float *gains, double *stats, void *workspace, int64_t N, int leaf,
-                        int depth, double angle, int compute_error, double momentum, double lr, double min_gain, bool step, hipStream_t s)
-{
-    const ATreePlan p = atree_plan(N, leaf, depth);
-    const int rc = atree_repulsion_launch(Y, order, skeys, nullptr, workspace, p, N, angle, s);
-    if (rc != VCY_OK) return rc;
-    char *w = (char *)workspace;
-    double *part = (double *)(w + p.part_off), *zpart = (double *)(w + p.zpart_off), *blk = (double *)(w + p.blk_off);
-    const int n = (int)N;
-    if (step)
-        hipLaunchKernelGGL((k_tsne_step<2, true>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
-                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
-    else
-        hipLaunchKernelGGL((k_tsne_step<2, false>), dim3(p.nb), dim3(TSNE_TPB), 0, s, Y, Yout, indptr, indices, pval, part, zpart, p.tb, 1, grad,
-                           update, gains, blk, stats, n, compute_error, momentum, lr, (float)min_gain);
-    VCY_LAUNCH_CHECK();
-    if (compute_error) {
-        hipLaunchKernelGGL(k_tsne_stats, dim3(1), dim3(TSNE_TPB), 0, s, blk, p.nb, stats);
-        VCY_LAUNCH_CHECK();
-    }
     return VCY_OK;
 }
 
@@ -1108,13 +1107,40 @@ static bool atree_in_range(int64_t N, int leaf, int depth)
 
 static int atree_check(int64_t N, int n_components, int leaf, int depth, double angle, const char *who)
 {
-    if (n_components != 2) return fail(VCY_ERR_UNSUPPORTED, "%s: the tree repulsion covers n_components == 2 only", who);
-    if (!(N >= 2 && N < (1ll << 30))) return fail(VCY_ERR_INVALID, "%s: N out of range", who);
+    const int rc = tree_check_shared(N, n_components, angle, who);
+    if (rc != VCY_OK) return rc;
     if (leaf < 1) return fail(VCY_ERR_INVALID, "%s: leaf_size must be >= 1", who);
     if (depth < 1 || depth > ATREE_MAX_DEPTH) return fail(VCY_ERR_INVALID, "%s: max_depth must be 1 .. 24", who);
     if (!atree_in_range(N, leaf, depth)) return fail(VCY_ERR_INVALID, "%s: the node bound of N, leaf_size and max_depth exceeds 2^31", who);
-    if (!(angle >= 0.0 && angle <= 1.0)) return fail(VCY_ERR_INVALID, "%s: angle must be in [0, 1]", who);
     return VCY_OK;
+}
+
+// both trees' _gradient and _step after the checks: the build and walk of the plan's tree, then the tail on the one split they leave
+template <class Plan, class Key>
+static int tree_eval(const TsneArgs &a, const int64_t *order, const Key *skeys, void *workspace, const Plan &p, int64_t N, double angle,
+                     hipStream_t s)
+{
+    const int rc = tree_repulsion_launch(a.Y, order, skeys, nullptr, workspace, p, N, angle, s);
+    if (rc != VCY_OK) return rc;
+    char *w = (char *)workspace;
+    return tsne_tail<2>(a, (const double *)(w + p.t.part_off), (const double *)(w + p.t.zpart_off), p.t.tb, 1, (double *)(w + p.t.blk_off),
+                        p.t.nb, (int)N, s);
+}
+
+static int tree_entry(const TsneArgs &a, const int64_t *order, const int32_t *skeys, void *workspace, int64_t N, int n_components, int depth,
+                      double angle, const char *who, hipStream_t s)
+{
+    int rc = tsne_args_check(a, order && skeys && workspace, who);
+    if (rc == VCY_OK) rc = tree_check(N, n_components, depth, angle, who);
+    return rc != VCY_OK ? rc : tree_eval(a, order, skeys, workspace, tree_plan(N, depth), N, angle, s);
+}
+
+static int atree_entry(const TsneArgs &a, const int64_t *order, const int64_t *skeys, void *workspace, int64_t N, int n_components, int leaf,
+                       int depth, double angle, const char *who, hipStream_t s)
+{
+    int rc = tsne_args_check(a, order && skeys && workspace, who);
+    if (rc == VCY_OK) rc = atree_check(N, n_components, leaf, depth, angle, who);
+    return rc != VCY_OK ? rc : tree_eval(a, order, skeys, workspace, atree_plan(N, leaf, depth), N, angle, s);
 }
 
 }  // namespace vcy
@@ -1141,23 +1167,16 @@ extern "C" size_t vcy_tsne_workspace_bytes(int64_t N, int n_components)
 extern "C" int vcy_tsne_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, float *grad, double *stats,
                                  void *workspace, int64_t N, int n_components, int compute_error, vcy_stream stream)
 {
-    VCY_REQUIRE(Y && indptr && indices && pval && grad && stats && workspace, "tsne_gradient: null pointer");
-    VCY_REQUIRE(N >= 2 && N < (1ll << 30), "tsne_gradient: N out of range");
-    VCY_REQUIRE(n_components >= 1 && n_components <= 3, "tsne_gradient: n_components must be 1, 2 or 3");
-    return tsne_dispatch(Y, nullptr, indptr, indices, pval, grad, nullptr, nullptr, stats, workspace, N, n_components, compute_error, 0.0, 0.0,
-                         0.0, false, (hipStream_t)stream);
+    const TsneArgs a = {Y, nullptr, indptr, indices, pval, grad, nullptr, nullptr, stats, compute_error, 0.0, 0.0, 0.0, false};
+    return tsne_entry(a, workspace, N, n_components, "tsne_gradient", (hipStream_t)stream);
 }
 
 extern "C" int vcy_tsne_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval, double *update,
                              float *gains, double *stats, void *workspace, int64_t N, int n_components, double momentum, double learning_rate,
                              double min_gain, int compute_error, vcy_stream stream)
 {
-    VCY_REQUIRE(Y && Y_out && indptr && indices && pval && update && gains && stats && workspace, "tsne_step: null pointer");
-    VCY_REQUIRE(Y != Y_out, "tsne_step: Y_out must not alias Y (the attraction reads every row's old position)");
-    VCY_REQUIRE(N >= 2 && N < (1ll << 30), "tsne_step: N out of range");
-    VCY_REQUIRE(n_components >= 1 && n_components <= 3, "tsne_step: n_components must be 1, 2 or 3");
-    return tsne_dispatch(Y, Y_out, indptr, indices, pval, nullptr, update, gains, stats, workspace, N, n_components, compute_error, momentum,
-                         learning_rate, min_gain, true, (hipStream_t)stream);
+    const TsneArgs a = {Y, Y_out, indptr, indices, pval, nullptr, update, gains, stats, compute_error, momentum, learning_rate, min_gain, true};
+    return tsne_entry(a, workspace, N, n_components, "tsne_step", (hipStream_t)stream);
 }
 
 extern "C" int vcy_tsne_tree_depth(int64_t N)
@@ -1170,7 +1189,7 @@ extern "C" int vcy_tsne_tree_depth(int64_t N)
 extern "C" size_t vcy_tsne_tree_workspace_bytes(int64_t N, int depth)
 {
     if (N < 2 || N >= (1ll << 30) || depth < 1 || depth > TREE_MAX_DEPTH) return 0;
-    return tree_plan(N, depth).bytes;
+    return tree_plan(N, depth).t.bytes;
 }
 
 extern "C" int vcy_tsne_tree_keys(const float *Y, int32_t *keys, void *workspace, int64_t N, int depth, vcy_stream stream)
@@ -1181,9 +1200,9 @@ extern "C" int vcy_tsne_tree_keys(const float *Y, int32_t *keys, void *workspace
     const TreePlan p = tree_plan(N, depth);
     char *w = (char *)workspace;
     float4 *boxp = (float4 *)(w + p.boxp_off);
-    hipLaunchKernelGGL(k_tree_box, dim3(p.nbx), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, (int)N);
+    hipLaunchKernelGGL(k_tree_box, dim3(p.t.nbx), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, (int)N);
     VCY_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tree_keys, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, p.nbx, (TreeHead *)w, keys, (int)N, depth);
+    hipLaunchKernelGGL(k_tree_keys, dim3(p.t.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, p.t.nbx, (TreeHead *)w, keys, (int)N, depth);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
 }
@@ -1196,23 +1215,15 @@ extern "C" int vcy_tsne_tree_repulsion(const float *Y, const int64_t *order, con
     if (rc != VCY_OK) return rc;
     const TreePlan p = tree_plan(N, depth);
     const int rc2 = tree_repulsion_launch(Y, order, sorted_keys, visits, workspace, p, N, angle, (hipStream_t)stream);
-    if (rc2 != VCY_OK) return rc2;
-    char *w = (char *)workspace;
-    hipLaunchKernelGGL(k_tree_rep_out, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const double *)(w + p.part_off),
-                       (const double *)(w + p.zpart_off), p.tb, rep, Z, (int)N);
-    VCY_LAUNCH_CHECK();
-    return VCY_OK;
+    return rc2 != VCY_OK ? rc2 : tree_rep_out(p.t, workspace, rep, Z, N, (hipStream_t)stream);
 }
 
 extern "C" int vcy_tsne_tree_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
                                       const int32_t *sorted_keys, float *grad, double *stats, void *workspace, int64_t N, int n_components,
                                       int depth, double angle, int compute_error, vcy_stream stream)
 {
-    VCY_REQUIRE(Y && indptr && indices && pval && order && sorted_keys && grad && stats && workspace, "tsne_tree_gradient: null pointer");
-    const int rc = tree_check(N, n_components, depth, angle, "tsne_tree_gradient");
-    if (rc != VCY_OK) return rc;
-    return tree_launch(Y, nullptr, indptr, indices, pval, order, sorted_keys, grad, nullptr, nullptr, stats, workspace, N, depth, angle,
-                       compute_error, 0.0, 0.0, 0.0, false, (hipStream_t)stream);
+    const TsneArgs a = {Y, nullptr, indptr, indices, pval, grad, nullptr, nullptr, stats, compute_error, 0.0, 0.0, 0.0, false};
+    return tree_entry(a, order, sorted_keys, workspace, N, n_components, depth, angle, "tsne_tree_gradient", (hipStream_t)stream);
 }
 
 extern "C" int vcy_tsne_tree_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval,
@@ -1220,18 +1231,14 @@ extern "C" int vcy_tsne_tree_step(const float *Y, float *Y_out, const int64_t *i
                                   int64_t N, int n_components, int depth, double angle, double momentum, double learning_rate, double min_gain,
                                   int compute_error, vcy_stream stream)
 {
-    VCY_REQUIRE(Y && Y_out && indptr && indices && pval && order && sorted_keys && update && gains && stats && workspace, "tsne_tree_step: null pointer");
-    VCY_REQUIRE(Y != Y_out, "tsne_tree_step: Y_out must not alias Y (the attraction reads every row's old position)");
-    const int rc = tree_check(N, n_components, depth, angle, "tsne_tree_step");
-    if (rc != VCY_OK) return rc;
-    return tree_launch(Y, Y_out, indptr, indices, pval, order, sorted_keys, nullptr, update, gains, stats, workspace, N, depth, angle,
-                       compute_error, momentum, learning_rate, min_gain, true, (hipStream_t)stream);
+    const TsneArgs a = {Y, Y_out, indptr, indices, pval, nullptr, update, gains, stats, compute_error, momentum, learning_rate, min_gain, true};
+    return tree_entry(a, order, sorted_keys, workspace, N, n_components, depth, angle, "tsne_tree_step", (hipStream_t)stream);
 }
 
 extern "C" size_t vcy_tsne_atree_workspace_bytes(int64_t N, int leaf_size, int max_depth)
 {
     if (!atree_in_range(N, leaf_size, max_depth)) return 0;
-    return atree_plan(N, leaf_size, max_depth).bytes;
+    return atree_plan(N, leaf_size, max_depth).t.bytes;
 }
 
 extern "C" int vcy_tsne_atree_keys(const float *Y, int64_t *keys, void *workspace, int64_t N, int leaf_size, int max_depth, vcy_stream stream)
@@ -1242,9 +1249,9 @@ extern "C" int vcy_tsne_atree_keys(const float *Y, int64_t *keys, void *workspac
     const ATreePlan p = atree_plan(N, leaf_size, max_depth);
     char *w = (char *)workspace;
     float4 *boxp = (float4 *)(w + p.boxp_off);
-    hipLaunchKernelGGL(k_tree_box, dim3(p.nbx), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, (int)N);
+    hipLaunchKernelGGL(k_tree_box, dim3(p.t.nbx), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, (int)N);
     VCY_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_atree_keys, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, p.nbx, (ATreeHead *)w, keys, (int)N,
+    hipLaunchKernelGGL(k_atree_keys, dim3(p.t.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const float2 *)Y, boxp, p.t.nbx, (ATreeHead *)w, keys, (int)N,
                        max_depth, leaf_size);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
@@ -1257,24 +1264,16 @@ extern "C" int vcy_tsne_atree_repulsion(const float *Y, const int64_t *order, co
     const int rc = atree_check(N, 2, leaf_size, max_depth, angle, "tsne_atree_repulsion");
     if (rc != VCY_OK) return rc;
     const ATreePlan p = atree_plan(N, leaf_size, max_depth);
-    const int rc2 = atree_repulsion_launch(Y, order, sorted_keys, visits, workspace, p, N, angle, (hipStream_t)stream);
-    if (rc2 != VCY_OK) return rc2;
-    char *w = (char *)workspace;
-    hipLaunchKernelGGL(k_tree_rep_out, dim3(p.nb), dim3(TSNE_TPB), 0, (hipStream_t)stream, (const double *)(w + p.part_off),
-                       (const double *)(w + p.zpart_off), p.tb, rep, Z, (int)N);
-    VCY_LAUNCH_CHECK();
-    return VCY_OK;
+    const int rc2 = tree_repulsion_launch(Y, order, sorted_keys, visits, workspace, p, N, angle, (hipStream_t)stream);
+    return rc2 != VCY_OK ? rc2 : tree_rep_out(p.t, workspace, rep, Z, N, (hipStream_t)stream);
 }
 
 extern "C" int vcy_tsne_atree_gradient(const float *Y, const int64_t *indptr, const int32_t *indices, const float *pval, const int64_t *order,
                                        const int64_t *sorted_keys, float *grad, double *stats, void *workspace, int64_t N, int n_components,
                                        int leaf_size, int max_depth, double angle, int compute_error, vcy_stream stream)
 {
-    VCY_REQUIRE(Y && indptr && indices && pval && order && sorted_keys && grad && stats && workspace, "tsne_atree_gradient: null pointer");
-    const int rc = atree_check(N, n_components, leaf_size, max_depth, angle, "tsne_atree_gradient");
-    if (rc != VCY_OK) return rc;
-    return atree_launch(Y, nullptr, indptr, indices, pval, order, sorted_keys, grad, nullptr, nullptr, stats, workspace, N, leaf_size, max_depth,
-                        angle, compute_error, 0.0, 0.0, 0.0, false, (hipStream_t)stream);
+    const TsneArgs a = {Y, nullptr, indptr, indices, pval, grad, nullptr, nullptr, stats, compute_error, 0.0, 0.0, 0.0, false};
+    return atree_entry(a, order, sorted_keys, workspace, N, n_components, leaf_size, max_depth, angle, "tsne_atree_gradient", (hipStream_t)stream);
 }
 
 extern "C" int vcy_tsne_atree_step(const float *Y, float *Y_out, const int64_t *indptr, const int32_t *indices, const float *pval,
@@ -1282,10 +1281,6 @@ extern "C" int vcy_tsne_atree_step(const float *Y, float *Y_out, const int64_t *
                                    int64_t N, int n_components, int leaf_size, int max_depth, double angle, double momentum, double learning_rate,
                                    double min_gain, int compute_error, vcy_stream stream)
 {
-    VCY_REQUIRE(Y && Y_out && indptr && indices && pval && order && sorted_keys && update && gains && stats && workspace, "tsne_atree_step: null pointer");
-    VCY_REQUIRE(Y != Y_out, "tsne_atree_step: Y_out must not alias Y (the attraction reads every row's old position)");
-    const int rc = atree_check(N, n_components, leaf_size, max_depth, angle, "tsne_atree_step");
-    if (rc != VCY_OK) return rc;
-    return atree_launch(Y, Y_out, indptr, indices, pval, order, sorted_keys, nullptr, update, gains, stats, workspace, N, leaf_size, max_depth,
-                        angle, compute_error, momentum, learning_rate, min_gain, true, (hipStream_t)stream);
+    const TsneArgs a = {Y, Y_out, indptr, indices, pval, nullptr, update, gains, stats, compute_error, momentum, learning_rate, min_gain, true};
+    return atree_entry(a, order, sorted_keys, workspace, N, n_components, leaf_size, max_depth, angle, "tsne_atree_step", (hipStream_t)stream);
 }

@@ -1700,15 +1700,26 @@ def tsne_perplexity(sqd, perplexity: float) -> Tuple[torch.Tensor, torch.Tensor]
     return P, steps
 
 
-def _tsne_shapes(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor) -> Tuple[int, int]:
-    """What the t-SNE kernels index by: positions (N, d) f32 and P as CSR (indptr int64 (N + 1), indices int32, values f32)."""
+def _tsne_positions(Y: torch.Tensor) -> None:
     if Y.dim() != 2 or Y.dtype != torch.float32 or not Y.is_contiguous():
         raise ValueError("t-SNE positions must be a contiguous (N, n_components) float32 device tensor")
+
+
+def _tsne_shapes(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor) -> Tuple[int, int]:
+    """What the t-SNE kernels index by: positions (N, d) f32 and P as CSR (indptr int64 (N + 1), indices int32, values f32)."""
+    _tsne_positions(Y)
     N, d = Y.shape
     if (indptr.dtype != torch.int64 or indptr.numel() != N + 1 or indices.dtype != torch.int32 or pval.dtype != torch.float32
             or indices.numel() != pval.numel() or not (indptr.is_contiguous() and indices.is_contiguous() and pval.is_contiguous())):
         raise ValueError("t-SNE P must be CSR: indptr int64 (N + 1), indices int32 and values float32 of the same length")
     return N, d
+
+
+def _tsne_step_state(who: str, Y: torch.Tensor, Y_out: torch.Tensor, update: torch.Tensor, gains: torch.Tensor, stats: torch.Tensor) -> None:
+    """What an iteration writes, for the step of any repulsion (``who``: the caller, for the message)."""
+    if not (Y_out.shape == Y.shape and Y_out.dtype == torch.float32 and update.shape == Y.shape and update.dtype == torch.float64
+            and gains.shape == Y.shape and gains.dtype == torch.float32 and stats.numel() >= 4 and stats.dtype == torch.float64):
+        raise ValueError(f"{who}: Y_out (N, d) f32, update (N, d) f64, gains (N, d) f32 and stats (4) f64")
 
 
 def tsne_workspace(N: int, n_components: int) -> torch.Tensor:
@@ -1734,13 +1745,86 @@ def tsne_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, indice
     """One iteration of scikit-learn's _gradient_descent on that objective: Y_out = Y + update, update (f64) and gains (f32) in
     place; stats = [Z, KL, |grad * gains|^2, .] (KL and the norm only with compute_error)."""
     N, d = _tsne_shapes(Y, indptr, indices, pval)
-    if not (Y_out.shape == Y.shape and Y_out.dtype == torch.float32 and update.shape == Y.shape and update.dtype == torch.float64
-            and gains.shape == Y.shape and gains.dtype == torch.float32 and stats.numel() >= 4 and stats.dtype == torch.float64
-            and ws.numel() >= int(_lib.lib().vcy_tsne_workspace_bytes(N, d))):
-        raise ValueError("tsne_step: Y_out (N, d) f32, update (N, d) f64, gains (N, d) f32, stats (4) f64 and a workspace of tsne_workspace(N, d)")
+    _tsne_step_state("tsne_step", Y, Y_out, update, gains, stats)
+    if ws.numel() < int(_lib.lib().vcy_tsne_workspace_bytes(N, d)):
+        raise ValueError("tsne_step: the workspace must be that of tsne_workspace(N, d)")
     _lib.check(_lib.lib().vcy_tsne_step(Y.data_ptr(), Y_out.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), update.data_ptr(),
                                         gains.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, float(momentum), float(learning_rate),
                                         float(min_gain), int(compute_error), _stream()), "tsne_step")
+
+
+# The two tree repulsions differ, for the wrappers, in three things: the name (vcy_<name>_* in the library, <name>_* here and in
+# messages), the dtype of the Morton keys, and their parameters - (depth,) or (leaf_size, max_depth), which every entry point takes
+# in that order right after N (and n_components) - with the ranges that messages quote.
+_TSNE_TREE = ("tsne_tree", torch.int32, "depth 1 .. 11")
+_TSNE_ATREE = ("tsne_atree", torch.int64, "leaf_size >= 1, max_depth 1 .. 24, node bound 1 + 4 max_depth (N // (leaf_size + 1)) < 2^31")
+
+
+def _tree_fn(tree, what: str):
+    return getattr(_lib.lib(), f"vcy_{tree[0]}_{what}")
+
+
+def _tree_workspace(tree, params, N):
+    nbytes = int(_tree_fn(tree, "workspace_bytes")(int(N), *params))
+    if nbytes == 0:
+        raise ValueError(f"{tree[0]}_workspace: N = {N} (>= 2) or the parameters {params} out of range ({tree[2]})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
+
+
+def _tree_args(tree, params, Y, ws, order=None, sorted_keys=None) -> int:
+    name, key_dtype, ranges = tree
+    _tsne_positions(Y)
+    N = Y.shape[0]
+    need = int(_tree_fn(tree, "workspace_bytes")(N, *params))
+    if need == 0 or ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError(f"{name}: N >= 2, {ranges}, and the workspace that of {name}_workspace(N, ...)")
+    if order is not None and not (order.dtype == torch.int64 and order.numel() == N and order.is_contiguous() and sorted_keys.dtype == key_dtype
+                                  and sorted_keys.numel() == N and sorted_keys.is_contiguous()):
+        raise ValueError(f"{name}: order must be (N) int64 and sorted_keys (N) {key_dtype} ({name}_keys)")
+    if Y.shape[1] != 2:
+        raise NotImplementedError(f"{name}: the tree repulsion covers n_components == 2 only")
+    return N
+
+
+def _tree_keys(tree, params, Y, ws):
+    N = _tree_args(tree, params, Y, ws)
+    keys = torch.empty(N, dtype=tree[1], device=Y.device)
+    _lib.check(_tree_fn(tree, "keys")(Y.data_ptr(), keys.data_ptr(), ws.data_ptr(), N, *params, _stream()), f"{tree[0]}_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    return keys, order, skeys
+
+
+def _tree_repulsion(tree, params, Y, order, sorted_keys, ws, angle, visits):
+    N = _tree_args(tree, params, Y, ws, order, sorted_keys)
+    rep = torch.empty((N, 3), dtype=torch.float64, device=Y.device)
+    Z = torch.empty(1, dtype=torch.float64, device=Y.device)
+    vis = torch.empty((N, 2), dtype=torch.int32, device=Y.device) if visits else None
+    _lib.check(_tree_fn(tree, "repulsion")(Y.data_ptr(), order.data_ptr(), sorted_keys.data_ptr(), rep.data_ptr(), Z.data_ptr(),
+                                           vis.data_ptr() if visits else None, ws.data_ptr(), N, *params, float(angle), _stream()),
+               f"{tree[0]}_repulsion")
+    return rep, Z, vis
+
+
+def _tree_gradient(tree, params, Y, indptr, indices, pval, order, sorted_keys, ws, angle, compute_error):
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    _tree_args(tree, params, Y, ws, order, sorted_keys)
+    grad = torch.empty_like(Y)
+    stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
+    _lib.check(_tree_fn(tree, "gradient")(Y.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), order.data_ptr(),
+                                          sorted_keys.data_ptr(), grad.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, *params, float(angle),
+                                          int(compute_error), _stream()), f"{tree[0]}_gradient")
+    return grad, stats
+
+
+def _tree_step(tree, params, Y, Y_out, indptr, indices, pval, order, sorted_keys, update, gains, stats, ws, angle, momentum, learning_rate,
+               min_gain, compute_error) -> None:
+    N, d = _tsne_shapes(Y, indptr, indices, pval)
+    _tree_args(tree, params, Y, ws, order, sorted_keys)
+    _tsne_step_state(f"{tree[0]}_step", Y, Y_out, update, gains, stats)
+    _lib.check(_tree_fn(tree, "step")(Y.data_ptr(), Y_out.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), order.data_ptr(),
+                                      sorted_keys.data_ptr(), update.data_ptr(), gains.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, *params,
+                                      float(angle), float(momentum), float(learning_rate), float(min_gain), int(compute_error), _stream()),
+               f"{tree[0]}_step")
 
 
 def tsne_tree_depth(N: int) -> int:
@@ -1749,24 +1833,7 @@ def tsne_tree_depth(N: int) -> int:
 
 
 def tsne_tree_workspace(N: int, depth: int) -> torch.Tensor:
-    nbytes = int(_lib.lib().vcy_tsne_tree_workspace_bytes(int(N), int(depth)))
-    if nbytes == 0:
-        raise ValueError(f"tsne_tree_workspace: N = {N} (>= 2) or depth = {depth} (1 .. 11) out of range")
-    return torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
-
-
-def _tsne_tree_args(Y: torch.Tensor, ws: torch.Tensor, depth: int, order: Optional[torch.Tensor] = None,
-                    sorted_keys: Optional[torch.Tensor] = None) -> int:
-    if Y.dim() != 2 or Y.dtype != torch.float32 or not Y.is_contiguous():
-        raise ValueError("t-SNE positions must be a contiguous (N, n_components) float32 device tensor")
-    N = Y.shape[0]
-    need = int(_lib.lib().vcy_tsne_tree_workspace_bytes(N, int(depth)))
-    if need == 0 or ws.dtype != torch.uint8 or ws.numel() < need:
-        raise ValueError("t-SNE tree: depth must be 1 .. 11, N >= 2 and the workspace that of tsne_tree_workspace(N, depth)")
-    if order is not None and not (order.dtype == torch.int64 and order.numel() == N and order.is_contiguous() and sorted_keys.dtype == torch.int32
-                                  and sorted_keys.numel() == N and sorted_keys.is_contiguous()):
-        raise ValueError("t-SNE tree: order must be (N) int64 and sorted_keys (N) int32 (tsne_tree_keys)")
-    return N
+    return _tree_workspace(_TSNE_TREE, (int(depth),), N)
 
 
 def tsne_tree_keys(Y: torch.Tensor, ws: torch.Tensor, depth: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1774,58 +1841,29 @@ def tsne_tree_keys(Y: torch.Tensor, ws: torch.Tensor, depth: int) -> Tuple[torch
     point's leaf-cell Morton key is computed (vcy_tsne_tree_keys) and sorted (torch.sort, stable: plumbing, no host read).
     Returns (keys (N) int32, order (N) int64, sorted keys (N) int32); order, the sorted keys and the same workspace go to
     tsne_tree_repulsion / tsne_tree_gradient / tsne_tree_step."""
-    N = _tsne_tree_args(Y, ws, depth)
-    if Y.shape[1] != 2:
-        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
-    keys = torch.empty(N, dtype=torch.int32, device=Y.device)
-    _lib.check(_lib.lib().vcy_tsne_tree_keys(Y.data_ptr(), keys.data_ptr(), ws.data_ptr(), N, int(depth), _stream()), "tsne_tree_keys")
-    skeys, order = torch.sort(keys, stable=True)
-    return keys, order, skeys
+    return _tree_keys(_TSNE_TREE, (int(depth),), Y, ws)
 
 
 def tsne_tree_repulsion(Y: torch.Tensor, order: torch.Tensor, sorted_keys: torch.Tensor, ws: torch.Tensor, depth: int, angle: float,
                         visits: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """The Barnes-Hut repulsion alone: (rep (N, 3) f64 = force x, y and sum_j w_ij per point, Z (1) f64, visits (N, 2) int32 =
     accepted nodes and directly summed points per target, or None)."""
-    N = _tsne_tree_args(Y, ws, depth, order, sorted_keys)
-    if Y.shape[1] != 2:
-        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
-    rep = torch.empty((N, 3), dtype=torch.float64, device=Y.device)
-    Z = torch.empty(1, dtype=torch.float64, device=Y.device)
-    vis = torch.empty((N, 2), dtype=torch.int32, device=Y.device) if visits else None
-    _lib.check(_lib.lib().vcy_tsne_tree_repulsion(Y.data_ptr(), order.data_ptr(), sorted_keys.data_ptr(), rep.data_ptr(), Z.data_ptr(),
-                                                  vis.data_ptr() if visits else None, ws.data_ptr(), N, int(depth), float(angle), _stream()),
-               "tsne_tree_repulsion")
-    return rep, Z, vis
+    return _tree_repulsion(_TSNE_TREE, (int(depth),), Y, order, sorted_keys, ws, angle, visits)
 
 
 def tsne_tree_gradient(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
                        sorted_keys: torch.Tensor, ws: torch.Tensor, depth: int, angle: float,
                        compute_error: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """tsne_gradient with the tree repulsion at ``angle`` (0: the exact sum): (grad (N, 2) f32, stats (4) f64)."""
-    N, d = _tsne_shapes(Y, indptr, indices, pval)
-    _tsne_tree_args(Y, ws, depth, order, sorted_keys)
-    grad = torch.empty_like(Y)
-    stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
-    _lib.check(_lib.lib().vcy_tsne_tree_gradient(Y.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), order.data_ptr(),
-                                                 sorted_keys.data_ptr(), grad.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, int(depth),
-                                                 float(angle), int(compute_error), _stream()), "tsne_tree_gradient")
-    return grad, stats
+    return _tree_gradient(_TSNE_TREE, (int(depth),), Y, indptr, indices, pval, order, sorted_keys, ws, angle, compute_error)
 
 
 def tsne_tree_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
                    sorted_keys: torch.Tensor, update: torch.Tensor, gains: torch.Tensor, stats: torch.Tensor, ws: torch.Tensor, depth: int,
                    angle: float, momentum: float, learning_rate: float, min_gain: float = 0.01, compute_error: bool = False) -> None:
     """tsne_step with the tree repulsion at ``angle``; order and sorted_keys are tsne_tree_keys' of the same Y and workspace."""
-    N, d = _tsne_shapes(Y, indptr, indices, pval)
-    _tsne_tree_args(Y, ws, depth, order, sorted_keys)
-    if not (Y_out.shape == Y.shape and Y_out.dtype == torch.float32 and update.shape == Y.shape and update.dtype == torch.float64
-            and gains.shape == Y.shape and gains.dtype == torch.float32 and stats.numel() >= 4 and stats.dtype == torch.float64):
-        raise ValueError("tsne_tree_step: Y_out (N, 2) f32, update (N, 2) f64, gains (N, 2) f32 and stats (4) f64")
-    _lib.check(_lib.lib().vcy_tsne_tree_step(Y.data_ptr(), Y_out.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(),
-                                             order.data_ptr(), sorted_keys.data_ptr(), update.data_ptr(), gains.data_ptr(), stats.data_ptr(),
-                                             ws.data_ptr(), N, d, int(depth), float(angle), float(momentum), float(learning_rate),
-                                             float(min_gain), int(compute_error), _stream()), "tsne_tree_step")
+    _tree_step(_TSNE_TREE, (int(depth),), Y, Y_out, indptr, indices, pval, order, sorted_keys, update, gains, stats, ws, angle, momentum,
+               learning_rate, min_gain, compute_error)
 
 
 TSNE_ATREE_LEAF_SIZE = 32         # default leaf_size of the adaptive tree (DESIGN.md section 9 has the sweep)
@@ -1833,26 +1871,7 @@ TSNE_ATREE_MAX_DEPTH = 24         # key bits per axis: what a float32 position r
 
 
 def tsne_atree_workspace(N: int, leaf_size: int = TSNE_ATREE_LEAF_SIZE, max_depth: int = TSNE_ATREE_MAX_DEPTH) -> torch.Tensor:
-    nbytes = int(_lib.lib().vcy_tsne_atree_workspace_bytes(int(N), int(leaf_size), int(max_depth)))
-    if nbytes == 0:
-        raise ValueError(f"tsne_atree_workspace: N = {N} (>= 2), leaf_size = {leaf_size} (>= 1) or max_depth = {max_depth} (1 .. 24) out of range "
-                         "(or their node bound 1 + 4 max_depth (N // (leaf_size + 1)) does not fit 31 bits)")
-    return torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
-
-
-def _tsne_atree_args(Y: torch.Tensor, ws: torch.Tensor, leaf_size: int, max_depth: int, order: Optional[torch.Tensor] = None,
-                     sorted_keys: Optional[torch.Tensor] = None) -> int:
-    if Y.dim() != 2 or Y.dtype != torch.float32 or not Y.is_contiguous():
-        raise ValueError("t-SNE positions must be a contiguous (N, n_components) float32 device tensor")
-    N = Y.shape[0]
-    need = int(_lib.lib().vcy_tsne_atree_workspace_bytes(N, int(leaf_size), int(max_depth)))
-    if need == 0 or ws.dtype != torch.uint8 or ws.numel() < need:
-        raise ValueError("t-SNE adaptive tree: leaf_size must be >= 1, max_depth 1 .. 24, N >= 2 and the workspace that of "
-                         "tsne_atree_workspace(N, leaf_size, max_depth)")
-    if order is not None and not (order.dtype == torch.int64 and order.numel() == N and order.is_contiguous() and sorted_keys.dtype == torch.int64
-                                  and sorted_keys.numel() == N and sorted_keys.is_contiguous()):
-        raise ValueError("t-SNE adaptive tree: order and sorted_keys must be (N) int64 (tsne_atree_keys)")
-    return N
+    return _tree_workspace(_TSNE_ATREE, (int(leaf_size), int(max_depth)), N)
 
 
 def tsne_atree_keys(Y: torch.Tensor, ws: torch.Tensor, leaf_size: int = TSNE_ATREE_LEAF_SIZE,
@@ -1861,14 +1880,7 @@ def tsne_atree_keys(Y: torch.Tensor, ws: torch.Tensor, leaf_size: int = TSNE_ATR
     point's int64 Morton key of max_depth bits per axis is computed (vcy_tsne_atree_keys) and sorted (torch.sort, stable: plumbing,
     no host read).  Returns (keys, order, sorted keys), each (N) int64; order, the sorted keys and the same workspace go to
     tsne_atree_repulsion / tsne_atree_gradient / tsne_atree_step."""
-    N = _tsne_atree_args(Y, ws, leaf_size, max_depth)
-    if Y.shape[1] != 2:
-        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
-    keys = torch.empty(N, dtype=torch.int64, device=Y.device)
-    _lib.check(_lib.lib().vcy_tsne_atree_keys(Y.data_ptr(), keys.data_ptr(), ws.data_ptr(), N, int(leaf_size), int(max_depth), _stream()),
-               "tsne_atree_keys")
-    skeys, order = torch.sort(keys, stable=True)
-    return keys, order, skeys
+    return _tree_keys(_TSNE_ATREE, (int(leaf_size), int(max_depth)), Y, ws)
 
 
 def tsne_atree_repulsion(Y: torch.Tensor, order: torch.Tensor, sorted_keys: torch.Tensor, ws: torch.Tensor, angle: float,
@@ -1876,30 +1888,14 @@ def tsne_atree_repulsion(Y: torch.Tensor, order: torch.Tensor, sorted_keys: torc
                          visits: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """The Barnes-Hut repulsion on the adaptive tree alone: (rep (N, 3) f64 = force x, y and sum_j w_ij per point, Z (1) f64,
     visits (N, 2) int32 = accepted nodes and directly summed points per target, or None)."""
-    N = _tsne_atree_args(Y, ws, leaf_size, max_depth, order, sorted_keys)
-    if Y.shape[1] != 2:
-        raise NotImplementedError("the tree repulsion covers n_components == 2 only")
-    rep = torch.empty((N, 3), dtype=torch.float64, device=Y.device)
-    Z = torch.empty(1, dtype=torch.float64, device=Y.device)
-    vis = torch.empty((N, 2), dtype=torch.int32, device=Y.device) if visits else None
-    _lib.check(_lib.lib().vcy_tsne_atree_repulsion(Y.data_ptr(), order.data_ptr(), sorted_keys.data_ptr(), rep.data_ptr(), Z.data_ptr(),
-                                                   vis.data_ptr() if visits else None, ws.data_ptr(), N, int(leaf_size), int(max_depth),
-                                                   float(angle), _stream()), "tsne_atree_repulsion")
-    return rep, Z, vis
+    return _tree_repulsion(_TSNE_ATREE, (int(leaf_size), int(max_depth)), Y, order, sorted_keys, ws, angle, visits)
 
 
 def tsne_atree_gradient(Y: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
                         sorted_keys: torch.Tensor, ws: torch.Tensor, angle: float, leaf_size: int = TSNE_ATREE_LEAF_SIZE,
                         max_depth: int = TSNE_ATREE_MAX_DEPTH, compute_error: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """tsne_gradient with the adaptive-tree repulsion at ``angle`` (0: the exact sum): (grad (N, 2) f32, stats (4) f64)."""
-    N, d = _tsne_shapes(Y, indptr, indices, pval)
-    _tsne_atree_args(Y, ws, leaf_size, max_depth, order, sorted_keys)
-    grad = torch.empty_like(Y)
-    stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
-    _lib.check(_lib.lib().vcy_tsne_atree_gradient(Y.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(), order.data_ptr(),
-                                                  sorted_keys.data_ptr(), grad.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, d, int(leaf_size),
-                                                  int(max_depth), float(angle), int(compute_error), _stream()), "tsne_atree_gradient")
-    return grad, stats
+    return _tree_gradient(_TSNE_ATREE, (int(leaf_size), int(max_depth)), Y, indptr, indices, pval, order, sorted_keys, ws, angle, compute_error)
 
 
 def tsne_atree_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, pval: torch.Tensor, order: torch.Tensor,
@@ -1907,15 +1903,8 @@ def tsne_atree_step(Y: torch.Tensor, Y_out: torch.Tensor, indptr: torch.Tensor, 
                     momentum: float, learning_rate: float, min_gain: float = 0.01, compute_error: bool = False,
                     leaf_size: int = TSNE_ATREE_LEAF_SIZE, max_depth: int = TSNE_ATREE_MAX_DEPTH) -> None:
     """tsne_step with the adaptive-tree repulsion at ``angle``; order and sorted_keys are tsne_atree_keys' of the same Y and workspace."""
-    N, d = _tsne_shapes(Y, indptr, indices, pval)
-    _tsne_atree_args(Y, ws, leaf_size, max_depth, order, sorted_keys)
-    if not (Y_out.shape == Y.shape and Y_out.dtype == torch.float32 and update.shape == Y.shape and update.dtype == torch.float64
-            and gains.shape == Y.shape and gains.dtype == torch.float32 and stats.numel() >= 4 and stats.dtype == torch.float64):
-        raise ValueError("tsne_atree_step: Y_out (N, 2) f32, update (N, 2) f64, gains (N, 2) f32 and stats (4) f64")
-    _lib.check(_lib.lib().vcy_tsne_atree_step(Y.data_ptr(), Y_out.data_ptr(), indptr.data_ptr(), indices.data_ptr(), pval.data_ptr(),
-                                              order.data_ptr(), sorted_keys.data_ptr(), update.data_ptr(), gains.data_ptr(), stats.data_ptr(),
-                                              ws.data_ptr(), N, d, int(leaf_size), int(max_depth), float(angle), float(momentum),
-                                              float(learning_rate), float(min_gain), int(compute_error), _stream()), "tsne_atree_step")
+    _tree_step(_TSNE_ATREE, (int(leaf_size), int(max_depth)), Y, Y_out, indptr, indices, pval, order, sorted_keys, update, gains, stats, ws, angle,
+               momentum, learning_rate, min_gain, compute_error)
 
 
 def select_cells(M, keep) -> "CellMatrix":

@@ -195,6 +195,29 @@ class DeviceTSNE:
         self.n_iter_, self.kl_divergence_ = it, kl
         return Y
 
+    def _repulsion_calls(self, N: int, d: int, repulsion, angle, tree_depth, leaf_size):
+        """The repulsion, chosen once for N points in d dimensions, as what the optimiser and the objective call:
+        (step(Y, Y_next, csr, update, gains, stats, momentum, lr, min_gain, want), gradient(Y, csr) -> (grad, stats), whether the
+        positions and the objective are checked for being finite).  The workspace is made here; a tree's keys are taken per call."""
+        self._check_repulsion(repulsion, d, angle, tree_depth, leaf_size)
+        if repulsion != "tree":
+            ws = ops.tsne_workspace(N, d)
+            return (lambda Y, Y_next, csr, update, gains, stats, *opt: ops.tsne_step(Y, Y_next, *csr, update, gains, stats, ws, *opt),
+                    lambda Y, csr: ops.tsne_gradient(Y, *csr, compute_error=True, ws=ws), False)
+        if isinstance(tree_depth, str):
+            leaf = ops.TSNE_ATREE_LEAF_SIZE if leaf_size is None else int(leaf_size)
+            ws = ops.tsne_atree_workspace(N, leaf)
+            keys = lambda Y: ops.tsne_atree_keys(Y, ws, leaf)[1:]
+            return (lambda Y, Y_next, csr, update, gains, stats, *opt:
+                    ops.tsne_atree_step(Y, Y_next, *csr, *keys(Y), update, gains, stats, ws, angle, *opt, leaf_size=leaf),
+                    lambda Y, csr: ops.tsne_atree_gradient(Y, *csr, *keys(Y), ws, angle, leaf_size=leaf, compute_error=True), True)
+        depth = ops.tsne_tree_depth(N) if tree_depth is None else int(tree_depth)
+        ws = ops.tsne_tree_workspace(N, depth)
+        keys = lambda Y: ops.tsne_tree_keys(Y, ws, depth)[1:]
+        return (lambda Y, Y_next, csr, update, gains, stats, *opt:
+                ops.tsne_tree_step(Y, Y_next, *csr, *keys(Y), update, gains, stats, ws, depth, angle, *opt),
+                lambda Y, csr: ops.tsne_tree_gradient(Y, *csr, *keys(Y), ws, depth, angle, compute_error=True), True)
+
     def _gradient_descent(self, Y: torch.Tensor, csr, it: int, max_iter: int, momentum: float, n_iter_without_progress: int):
         """_gradient_descent (_t_sne.py:301-444) from positions Y (N, d) f32 on the device: fresh update and gains, one vcy_tsne_step
         per iteration on one stream; the host reads back [Z, KL, |grad|^2] only where scikit-learn computes the error (every 50th
@@ -202,41 +225,21 @@ class DeviceTSNE:
         repulsion="tree": per iteration the keys, their sort and vcy_tsne_tree_step (tree_depth="adaptive": vcy_tsne_atree_step); the
         read at a check also carries whether the new positions are finite, and a fit whose positions are not stops there with a
         FloatingPointError."""
-        indptr, indices, pval = csr
         N, d = Y.shape
-        tree = self.repulsion == "tree"
-        adaptive = tree and isinstance(self.tree_depth, str)
-        if tree:
-            self._check_repulsion(self.repulsion, d, self.angle, self.tree_depth, self.leaf_size)
-        if adaptive:
-            leaf = self._leaf_size(self.leaf_size)
-            tws = ops.tsne_atree_workspace(N, leaf)
-        elif tree:
-            depth = ops.tsne_tree_depth(N) if self.tree_depth is None else int(self.tree_depth)
-            tws = ops.tsne_tree_workspace(N, depth)
+        step, _, finite = self._repulsion_calls(N, d, self.repulsion, self.angle, self.tree_depth, self.leaf_size)
         update = torch.zeros((N, d), dtype=torch.float64, device=Y.device)
         gains = torch.ones((N, d), dtype=torch.float32, device=Y.device)
         Y_next = torch.empty_like(Y)
         stats = torch.zeros(4, dtype=torch.float64, device=Y.device)
-        ws = None if tree else ops.tsne_workspace(N, d)
         lr = float(self.learning_rate_)
         error = best_error = np.finfo(float).max
         best_iter = i = it
         for i in range(it, max_iter):
             check = (i + 1) % self._N_ITER_CHECK == 0
             want = check or i == max_iter - 1
-            if adaptive:
-                _, order, skeys = ops.tsne_atree_keys(Y, tws, leaf)
-                ops.tsne_atree_step(Y, Y_next, indptr, indices, pval, order, skeys, update, gains, stats, tws, self.angle, momentum, lr, 0.01,
-                                    want, leaf_size=leaf)
-            elif tree:
-                _, order, skeys = ops.tsne_tree_keys(Y, tws, depth)
-                ops.tsne_tree_step(Y, Y_next, indptr, indices, pval, order, skeys, update, gains, stats, tws, depth, self.angle, momentum, lr,
-                                   0.01, want)
-            else:
-                ops.tsne_step(Y, Y_next, indptr, indices, pval, update, gains, stats, ws, momentum, lr, 0.01, want)
+            step(Y, Y_next, csr, update, gains, stats, momentum, lr, 0.01, want)
             Y, Y_next = Y_next, Y
-            if want and tree:
+            if want and finite:
                 h = torch.cat([stats, torch.isfinite(Y).all().to(torch.float64).reshape(1)]).cpu().numpy()
                 if h[4] != 1.0 or not np.all(np.isfinite(h[:3])):
                     raise FloatingPointError(f"DeviceTSNE(repulsion='tree'): non-finite positions or objective at iteration {i}")
@@ -263,28 +266,12 @@ class DeviceTSNE:
                torch.from_numpy(np.asarray(P.data, dtype=np.float32)).to(dev))
         return Yd, csr
 
-    @staticmethod
-    def _leaf_size(leaf_size) -> int:
-        return ops.TSNE_ATREE_LEAF_SIZE if leaf_size is None else int(leaf_size)
-
     def _objective(self, Y, P, repulsion: str = "exact", angle: float = 0.5, tree_depth=None, leaf_size=None) -> Tuple[float, np.ndarray]:
         """(KL, grad (N, d) f32) for positions Y and a scipy CSR P (its values read as f32): of _kl_divergence_bh at angle = 0
         (repulsion="exact"), or with the tree repulsion at ``angle`` (repulsion="tree"; tree_depth="adaptive": the adaptive tree)."""
         Yd, csr = self._device_args(Y, P)
-        self._check_repulsion(repulsion, Yd.shape[1], angle, tree_depth, leaf_size)
-        if repulsion == "tree" and isinstance(tree_depth, str):
-            leaf = self._leaf_size(leaf_size)
-            tws = ops.tsne_atree_workspace(Yd.shape[0], leaf)
-            _, order, skeys = ops.tsne_atree_keys(Yd, tws, leaf)
-            grad, stats = ops.tsne_atree_gradient(Yd, *csr, order, skeys, tws, angle, leaf_size=leaf, compute_error=True)
-            return float(stats[1]), grad.cpu().numpy()
-        if repulsion == "tree":
-            depth = ops.tsne_tree_depth(Yd.shape[0]) if tree_depth is None else int(tree_depth)
-            tws = ops.tsne_tree_workspace(Yd.shape[0], depth)
-            _, order, skeys = ops.tsne_tree_keys(Yd, tws, depth)
-            grad, stats = ops.tsne_tree_gradient(Yd, *csr, order, skeys, tws, depth, angle, compute_error=True)
-            return float(stats[1]), grad.cpu().numpy()
-        grad, stats = ops.tsne_gradient(Yd, *csr, compute_error=True)
+        _, gradient, _ = self._repulsion_calls(*Yd.shape, repulsion, angle, tree_depth, leaf_size)
+        grad, stats = gradient(Yd, csr)
         return float(stats[1]), grad.cpu().numpy()
 
     def _descend(self, Y0, P, it: int, max_iter: int, momentum: float, n_iter_without_progress: int = 300):
