@@ -77,7 +77,8 @@ const char *vcy_last_error(void);
  * against (velocyto_amd/_lib.py: EXPECTED_ABI).  (Round 7 added the enumerator VCY_RULES_PARTIAL_ROOT2: no argument list changed and every
  * value a version-4 caller passes is still accepted, so the version stays; such a caller's VCY_RULES_PARTIAL on VCY_SQRT / VCY_F64 now gets
  * the one-correction root described at vcy_rules.)  (Gene selection from CSR layers added vcy_csr_gene_stats_block_cells,
- * vcy_csr_gene_stats_workspace_bytes, vcy_csr_gene_stats, vcy_csr_select_count and vcy_csr_select_fill: additions only, the version stays.) */
+ * vcy_csr_gene_stats_workspace_bytes, vcy_csr_gene_stats, vcy_csr_select_count and vcy_csr_select_fill: additions only, the version stays.
+ * So are the vcy_loom_tile_* entries and vcy_loom_block_host.) */
 int vcy_abi_version(void);
 /* Number of CUs / LDS bytes per workgroup of the current device (host query). */
 int vcy_device_info(int *cu_count, int *lds_bytes_per_block, int64_t *hbm_bytes);
@@ -771,6 +772,42 @@ int vcy_csr_select_count(const int64_t *indptr, const int32_t *indices, const in
                          vcy_stream stream);
 int vcy_csr_select_fill(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *remap, const int64_t *indptr_out,
                         int32_t *indices_out, void *data_out, int64_t C, int64_t G, int count_dtype, vcy_stream stream);
+
+/* ---------------------------------------------------------------- upstream caller: .loom ingest in blocks of cells
+ * VelocytoLoom.__init__ (analysis.py:56-67) reads /layers/spliced, unspliced, ambiguous whole, as float64, and sums them per cell.  Here
+ * a layer arrives in blocks of cells, each a gene-major tile on the device in the FILE's element type: G rows (genes) of B cells, row
+ * stride ldt >= B elements, elem_type one of the vcy_loom_elem codes below; a uint64 layer is not taken.  The tile is read once per launch.
+ * result (4 int64): [any element that is not an integer (NaN, +-inf included; they set this flag only), any negative, any above 65535,
+ * the largest element clamped to 0 .. 2^62].  -0.0 is a zero; a stored zero counts in nothing.  sums / data mean something only when
+ * the three flags are clear (a non-zero element that is no count is carried as 65535, so count and fill always agree on the structure).
+ * workspace: vcy_loom_tile_workspace_bytes(G, B) bytes, 8-byte aligned; it carries the per-slab counts (slabs of
+ * vcy_loom_tile_slab_genes() genes) from vcy_loom_tile_count to vcy_loom_tile_fill, so the same buffer goes to both, untouched between.
+ * vcy_loom_tile_count: nnz[c] (B int64) = non-zero elements of cell c of the tile, sums[c] (B int64) = its counts added up (exact).
+ * vcy_loom_tile_fill: writes cell c's non-zeros at row_start[c] .. row_start[c + 1] - 1 of indices (int32 gene numbers, ascending
+ * inside the cell's row) and data (uint16 bits); row_start (B + 1 int64) are ABSOLUTE positions in arrays of `capacity` elements -
+ * the block's cumulative nnz plus wherever the block starts.  Nothing outside those ranges is written, and every position is clamped
+ * to [0, capacity) whatever row_start and the workspace hold.
+ * vcy_loom_tile_dense: the converting transpose - rows s .. s + B - 1 of the cells-major (C, ld) uint16 matrix `out` (ld >= G, even),
+ * columns G .. ld - 1 written as zeros - with sums and result as vcy_loom_tile_count.  workspace: vcy_loom_tile_workspace_bytes(ld, B).
+ * vcy_loom_block_host (host pointers, no device work): fills such a tile for the cells c0 .. c1 - 1 from the chunks of a chunked
+ * (G, C) dataset of chunk_rows x chunk_cols chunks.  hdf5_calls = the addresses of { H5Dget_chunk_storage_size, H5Dread_chunk,
+ * H5Eset_auto2 or NULL, H5Eclear2 or NULL } of the HDF5 library that opened `dset` (this library does not link HDF5; its thread-safe build is required
+ * for threads > 1).  filters = 0 none, 1 deflate, 2 shuffle + deflate, the per-chunk filter mask honoured; a chunk that was never
+ * written (no storage size) reads as zeros.  1 .. 16 threads of the call's own fetch the stored bytes, inflate, unshuffle and place
+ * the rows, cropped to the dataset and the block; with the last two given they silence and clear the HDF5 error stack of those threads.
+ * Returns -4 when a chunk does not inflate to the chunk size, -5 when it cannot be read; *bad_chunk = (chunk row) * ncc +
+ * (chunk column - c0 / chunk_cols), ncc = the chunk columns the block touches.                                                  */
+typedef enum { VCY_LOOM_U8 = 0, VCY_LOOM_U16 = 1, VCY_LOOM_U32 = 2, VCY_LOOM_I32 = 3, VCY_LOOM_I64 = 4, VCY_LOOM_F32 = 5, VCY_LOOM_F64 = 6 } vcy_loom_elem;
+int64_t vcy_loom_tile_slab_genes(void);
+size_t vcy_loom_tile_workspace_bytes(int64_t G, int64_t B);
+int vcy_loom_tile_count(const void *tile, int64_t *nnz, int64_t *sums, int64_t *result, void *workspace, int64_t G, int64_t B, int64_t ldt,
+                        int elem_type, vcy_stream stream);
+int vcy_loom_tile_fill(const void *tile, const void *workspace, const int64_t *row_start, int32_t *indices, void *data, int64_t capacity,
+                       int64_t G, int64_t B, int64_t ldt, int elem_type, vcy_stream stream);
+int vcy_loom_tile_dense(const void *tile, void *out, int64_t *sums, int64_t *result, void *workspace, int64_t G, int64_t B, int64_t ldt,
+                        int elem_type, int64_t s, int64_t C, int64_t ld, vcy_stream stream);
+int vcy_loom_block_host(void *const *hdf5_calls, int64_t dset, int64_t G, int64_t C, int64_t chunk_rows, int64_t chunk_cols, int elem_size,
+                        int filters, int64_t c0, int64_t c1, void *tile, int64_t ldt, int threads, int64_t *bad_chunk);
 
 /* ---------------------------------------------------------------- host helper: neighbour sampling of estimate_transition_prob
  * analysis.py:1561-1564 draws, per cell, np.random.choice(n, size, replace=False, p=p) from numpy's legacy global RNG.  This is

@@ -116,6 +116,12 @@ SIGNATURES = {
     "vcy_csr_gene_stats": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
     "vcy_csr_select_count": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "vcy_csr_select_fill": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
+    "vcy_loom_tile_slab_genes": (c_i64, []),
+    "vcy_loom_tile_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vcy_loom_tile_count": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_loom_tile_fill": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_loom_tile_dense": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_vp]),
+    "vcy_loom_block_host": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_i64, c_i64, c_vp, c_i64, c_int, c_vp]),
     "vcy_quantile_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_gene_quantiles": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_dbl), c_int, c_vp, c_vp, c_i64,
                                    c_i64, c_i64, c_int, c_vp]),
@@ -191,7 +197,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
         objs = list(ex.map(cc, sources()))
-    r = subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", LIB_PATH], capture_output=True, text=True)
+    r = subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", LIB_PATH, "-lz"], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stderr}")
     return LIB_PATH

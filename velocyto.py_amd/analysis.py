@@ -61,11 +61,19 @@ class VelocytoLoom(PreprocessMixin):
         object.__setattr__(self, "_dtype", ops.resolve_dtype(None))
         return self
 
-    def __init__(self, loom_filepath: str = None, dtype=None) -> None:
+    def __init__(self, loom_filepath: str = None, dtype=None, ingest: str = "whole") -> None:
+        """ingest="whole": every layer is read onto the host in one piece, uploaded and transposed (analysis.py:56-64).
+        ingest="stream" (opt-in): the layers arrive in blocks of cells, inflated on host threads and converted on the device
+        (loom_io.LayerBlockReader, ops.counts_from_tiles); every attribute comes out as with "whole", bit for bit."""
         object.__setattr__(self, "_dtype", ops.resolve_dtype(dtype))
+        if ingest not in ("whole", "stream"):
+            raise ValueError(f"ingest must be 'whole' or 'stream', got {ingest!r}")
         if loom_filepath is not None:
             from .loom_io import read_loom
             self.loom_filepath = loom_filepath
+            if ingest == "stream":
+                self._init_layers_streamed(loom_filepath)
+                return
             layers, ca, ra = read_loom(loom_filepath)                 # analysis.py:56-64
             self._init_layers(layers["spliced"], layers["unspliced"], layers.get("ambiguous"), ca, ra)
 
@@ -84,6 +92,39 @@ class VelocytoLoom(PreprocessMixin):
         self.ra = dict(ra) if ra is not None else {"Gene": np.arange(self.dev("S").G)}
         self.initial_cell_size = ops.row_sums(self.dev("S")).cpu().numpy()      # analysis.py:66-67
         self.initial_Ucell_size = ops.row_sums(self.dev("U")).cpu().numpy()
+
+    def _init_layers_streamed(self, path: str) -> None:
+        """_init_layers with the layers read in cell blocks (analysis.py:56-67).  A layer the kernels report as no count layer
+        (non-integer, negative, above 65535) - or of an element type they do not take - is read whole instead, as
+        ingest="whole" reads it."""
+        import logging
+        from . import loom_io
+        names, ca, ra = loom_io.read_loom_attrs(path)
+        sizes = {}
+        for attr, layer in (("S", "spliced"), ("U", "unspliced"), ("A", "ambiguous")):
+            if layer not in names:
+                continue
+            counts = None
+            with loom_io.LayerBlockReader(path, layer) as reader:
+                if reader.dtype in ops.LOOM_ELEM and reader.G > 0 and reader.C > 0:
+                    counts, sums, res = ops.counts_from_tiles(reader)
+                    if res[:, :3].any():
+                        counts = None
+                is_float = reader.dtype.kind == "f"
+            if counts is None:
+                logging.info("layer %s of %s is not a count layer the streamed ingest takes: read whole", layer, path)
+                setattr(self, attr, loom_io.read_layer(path, layer))
+                continue
+            if not is_float and int(res[:, 3].max()) <= 255:          # CountMatrix.from_genes_major narrows such a layer
+                counts = ops.CountMatrix(counts.t.to(torch.uint8), counts.G)
+            # an integer S / U layer keeps its counts (self._counts), as when assigned from the file's integer array; a float
+            # layer holding integers, and A, become float matrices only
+            setattr(self, attr, counts if attr in ("S", "U") and not is_float else counts.to_float(self._dtype))
+            sizes[attr] = sums.double().cpu().numpy()                 # integers below 2^53: the f64 row sums, exactly
+        self.ca = dict(ca)
+        self.ra = dict(ra)
+        self.initial_cell_size = sizes["S"] if "S" in sizes else ops.row_sums(self.dev("S")).cpu().numpy()      # analysis.py:66-67
+        self.initial_Ucell_size = sizes["U"] if "U" in sizes else ops.row_sums(self.dev("U")).cpu().numpy()
 
     # ------------------------------------------------------------------ attribute plumbing
     def dev(self, name: str) -> CellMatrix:

@@ -72,7 +72,19 @@ def _lib():
                 ("H5Aget_num_attrs", ctypes.c_int, [hid_t]),
                 ("H5Aopen_by_idx", hid_t, [hid_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, hsize_t, hid_t, hid_t]),
                 ("H5Aget_name", ctypes.c_ssize_t, [hid_t, ctypes.c_size_t, ctypes.c_char_p]), ("H5Aget_type", hid_t, [hid_t]),
-                ("H5Aget_space", hid_t, [hid_t]), ("H5Aread", ctypes.c_int, [hid_t, hid_t, ctypes.c_void_p]), ("H5Aclose", ctypes.c_int, [hid_t])):
+                ("H5Aget_space", hid_t, [hid_t]), ("H5Aread", ctypes.c_int, [hid_t, hid_t, ctypes.c_void_p]), ("H5Aclose", ctypes.c_int, [hid_t]),
+                # what LayerBlockReader asks about a layer's storage
+                ("H5Dget_create_plist", hid_t, [hid_t]),
+                ("H5Pget_layout", ctypes.c_int, [hid_t]), ("H5Pget_chunk", ctypes.c_int, [hid_t, ctypes.c_int, ctypes.POINTER(hsize_t)]),
+                ("H5Pget_nfilters", ctypes.c_int, [hid_t]),
+                ("H5Pget_filter2", ctypes.c_int, [hid_t, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_size_t),
+                                                  ctypes.POINTER(ctypes.c_uint), ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint)]),
+                ("H5Pfill_value_defined", ctypes.c_int, [hid_t, ctypes.POINTER(ctypes.c_int)]),
+                ("H5Pget_fill_value", ctypes.c_int, [hid_t, hid_t, ctypes.c_void_p]),
+                ("H5Tget_order", ctypes.c_int, [hid_t]),
+                ("H5Pset_shuffle", ctypes.c_int, [hid_t]), ("H5is_library_threadsafe", ctypes.c_int, [ctypes.POINTER(ctypes.c_bool)]),
+                ("H5Dget_chunk_storage_size", ctypes.c_int, [hid_t, ctypes.POINTER(hsize_t), ctypes.POINTER(hsize_t)]),
+                ("H5Dread_chunk", ctypes.c_int, [hid_t, hid_t, ctypes.POINTER(hsize_t), ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p])):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         L._native = {k: hid_t.in_dll(L, f"H5T_NATIVE_{k}_g").value for k in
@@ -283,14 +295,289 @@ def read_layer_block(path: str, layer: str, c0: int, c1: int) -> np.ndarray:
         L.H5Fclose(f)
 
 
-def read_layer_csr(path: str, layer: str, cell_block: int = 8192, c0: int = 0, c1: Optional[int] = None):
+def read_loom_attrs(path: str) -> Tuple[Tuple[str, ...], Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+    """-> (names under /layers, col_attrs, row_attrs): what read_loom returns beside the layers, without reading a layer."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    L = _lib()
+    f = _check(L.H5Fopen(path.encode(), H5F_ACC_RDONLY, H5P_DEFAULT), f"open {path}")
+    try:
+        g, names = _group_members(L, f, "layers")
+        if g is None or "spliced" not in names or "unspliced" not in names:
+            raise IOError(f"{path}: not a velocyto loom file (needs /layers/spliced and /layers/unspliced)")
+        L.H5Gclose(g)
+        attrs = []
+        for grp in ("col_attrs", "row_attrs"):
+            g, members = _group_members(L, f, grp)
+            attrs.append({k: _read_dataset(L, g, k) for k in members} if g is not None else {})
+            if g is not None:
+                L.H5Gclose(g)
+        return tuple(names), attrs[0], attrs[1]
+    finally:
+        L.H5Fclose(f)
+
+
+def read_layer(path: str, layer: str) -> np.ndarray:
+    """/layers/<layer> whole, as stored (genes x cells): one H5Dread, what read_loom does per layer."""
+    L = _lib()
+    f = _check(L.H5Fopen(path.encode(), H5F_ACC_RDONLY, H5P_DEFAULT), f"open {path}")
+    try:
+        g = _check(L.H5Gopen2(f, b"layers", H5P_DEFAULT), "open group layers")
+        try:
+            return _read_dataset(L, g, layer)
+        finally:
+            L.H5Gclose(g)
+    finally:
+        L.H5Fclose(f)
+
+
+H5D_CHUNKED, H5Z_FILTER_DEFLATE, H5Z_FILTER_SHUFFLE = 2, 1, 2
+READER_THREADS, READER_MAX_THREADS = 8, 16        # never os.cpu_count(): a job is given a few CPUs of a much larger machine
+
+
+class LayerBlockReader:
+    """Iterator over ``(s, e, tile)``: the cells s..e-1 of /layers/<layer>, all genes, as a C-contiguous ``(G, e - s)`` array in
+    the FILE's element type - the bytes read_layer_block(path, layer, s, e) returns - for s = c0, c0 + cell_block, ... < c1.
+
+    The block's chunks are found (dataset creation plist: H5Pget_chunk), their stored bytes fetched (H5Dread_chunk), inflated and
+    placed on `threads` host threads (vcy_loom_block_host: C++ threads, because a Python loop over 16 KB chunks is
+    bound by the interpreter lock, not by zlib), while the caller works on the block before: a background thread keeps one
+    block ahead.  threads=None means 8; at most 16 are used.
+
+    Storage taken directly: chunked layout, rank 2, little-endian integer or IEEE float elements of 1, 2, 4 or 8 bytes, filter
+    pipeline empty, deflate or shuffle + deflate (the per-chunk filter mask honoured), fill value zero (a chunk
+    that was never written reads as zeros).  Anything else - contiguous layout, other filters, big-endian, a non-zero fill value -
+    is read block by block with read_layer_block into the same buffers: never an error (`direct` says which).  A chunk that does
+    not inflate to the chunk size raises IOError naming the chunk.
+
+    Buffers.  Tiles live in two staging buffers, allocated once (page-locked when a GPU is present, so the upload can be
+    asynchronous) and used alternately.  A tile is valid until the caller asks for the next block: at that point its buffer is
+    handed back, and the reader fills it with the block after the next one.  A caller that copies a tile asynchronously records
+    an event behind the copy and passes it to ``copied(event)`` before it asks for the next block: the reader then waits for
+    that event (``event.synchronize()``) before it writes into the buffer again - a buffer is overwritten after the consumer's
+    copy event, never before."""
+
+    def __init__(self, path: str, layer: str, cell_block: int = 8192, c0: int = 0, c1: Optional[int] = None, threads: Optional[int] = None):
+        import threading
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        self.path, self.layer = path, layer
+        self.cell_block = int(cell_block)
+        if self.cell_block < 1:
+            raise ValueError("cell_block must be positive")
+        self.threads = max(1, min(READER_MAX_THREADS, READER_THREADS if threads is None else int(threads)))
+        L = self._L = _lib()
+        self._f = self._d = None
+        self._thread = None
+        self._f = _check(L.H5Fopen(path.encode(), H5F_ACC_RDONLY, H5P_DEFAULT), f"open {path}")
+        try:
+            self._d = _check(L.H5Dopen2(self._f, f"layers/{layer}".encode(), H5P_DEFAULT), f"open layer {layer}")
+            sp, tp = L.H5Dget_space(self._d), L.H5Dget_type(self._d)
+            nd = L.H5Sget_simple_extent_ndims(sp)
+            dims = (hsize_t * max(nd, 2))()
+            L.H5Sget_simple_extent_dims(sp, dims, None)
+            L.H5Sclose(sp)
+            try:
+                if nd != 2:
+                    raise IOError(f"layer {layer}: rank {nd}, expected (genes, cells)")
+                self.G, self.C = int(dims[0]), int(dims[1])
+                cls, size = L.H5Tget_class(tp), int(L.H5Tget_size(tp))
+                self.dtype = (np.dtype(np.float32 if size == 4 else np.float64) if cls == H5T_FLOAT
+                              else np.dtype(("u" if L.H5Tget_sign(tp) == 0 else "i") + str(size)))        # as read_layer_block
+                self.c0, self.c1 = int(c0), self.C if c1 is None else int(c1)
+                if not (0 <= self.c0 <= self.c1 <= self.C):
+                    raise IndexError(f"cells {self.c0}:{self.c1} outside 0:{self.C}")
+                self._plan(tp, cls, size)
+            finally:
+                L.H5Tclose(tp)
+        except BaseException:
+            self.close()
+            raise
+        self.width = max(1, min(self.cell_block, self.c1 - self.c0))
+        self._owners = []                                  # the page-locked tensors behind the buffers
+        self._buffers = [self._staging(self.G * self.width * self.dtype.itemsize) for _ in range(2)]
+        self._events = [None, None]
+        self._free = [threading.Semaphore(1), threading.Semaphore(1)]
+        self._held = None                                  # buffer of the tile handed out last
+        self._queue = None
+        self._stop = False
+
+    # ---- what the dataset's storage allows
+    def _plan(self, tp, cls, size) -> None:
+        L = self._L
+        self.direct, self.why_not = False, None
+        self.chunk, self.filters = None, 0
+
+        def no(why):
+            self.why_not = why
+
+        if cls not in (H5T_INTEGER, H5T_FLOAT) or size not in (1, 2, 4, 8) or (cls == H5T_FLOAT and size not in (4, 8)):
+            return no("element type")
+        if size > 1 and L.H5Tget_order(tp) != 0:
+            return no("big-endian")
+        if self.G == 0 or self.C == 0:
+            return no("empty dataset")
+        dcpl = L.H5Dget_create_plist(self._d)
+        try:
+            if L.H5Pget_layout(dcpl) != H5D_CHUNKED:
+                return no("layout is not chunked")
+            ch = (hsize_t * 2)()
+            if L.H5Pget_chunk(dcpl, 2, ch) != 2:
+                return no("chunk rank")
+            ids = []
+            for i in range(max(L.H5Pget_nfilters(dcpl), 0)):
+                flags, n, cfg = ctypes.c_uint(), ctypes.c_size_t(0), ctypes.c_uint()
+                ids.append(L.H5Pget_filter2(dcpl, i, ctypes.byref(flags), ctypes.byref(n), None, 0, None, ctypes.byref(cfg)))
+            if ids not in ([], [H5Z_FILTER_DEFLATE], [H5Z_FILTER_SHUFFLE, H5Z_FILTER_DEFLATE]):
+                return no(f"filter pipeline {ids}")
+            status = ctypes.c_int(-1)
+            if L.H5Pfill_value_defined(dcpl, ctypes.byref(status)) < 0 or status.value not in (1, 2):
+                return no("fill value undefined")
+            if status.value == 2:                          # set by the writer: only zero lets an unwritten chunk be skipped
+                fv = np.ones(1, dtype=self.dtype)
+                if L.H5Pget_fill_value(dcpl, L._native[_NP2H5[self.dtype]], fv.ctypes.data) < 0 or fv[0] != 0:
+                    return no("non-zero fill value")
+        finally:
+            L.H5Pclose(dcpl)
+        safe = ctypes.c_bool(False)
+        if self.threads > 1 and (L.H5is_library_threadsafe(ctypes.byref(safe)) < 0 or not safe.value):
+            return no("HDF5 library is not a thread-safe build")
+        from . import _lib as hip
+        self._hip = hip.lib()
+        # the stored bytes come through the library (H5Dread_chunk), so a user block needs no care; H5Dget_chunk_info_by_coord + pread
+        # is not used: that call of 1.10 walks the chunk index from its start (milliseconds per chunk in an atlas file)
+        self._calls = (ctypes.c_void_p * 4)(*(ctypes.cast(getattr(L, n), ctypes.c_void_p) for n in
+                                              ("H5Dget_chunk_storage_size", "H5Dread_chunk", "H5Eset_auto2", "H5Eclear2")))
+        self.chunk, self.filters, self.direct = (int(ch[0]), int(ch[1])), len(ids), True
+
+    def _staging(self, nbytes: int) -> np.ndarray:
+        try:
+            import torch
+            if torch.cuda.is_available():
+                t = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
+                self._owners.append(t)
+                return t.numpy()
+        except ImportError:
+            pass
+        return np.empty(max(nbytes, 1), dtype=np.uint8)
+
+    def blocks(self):
+        return [(s, min(self.c1, s + self.cell_block)) for s in range(self.c0, self.c1, self.cell_block)]
+
+    def _fill(self, buf: np.ndarray, s: int, e: int) -> np.ndarray:
+        tile = buf[: self.G * (e - s) * self.dtype.itemsize].view(self.dtype).reshape(self.G, e - s)
+        if not self.direct:
+            tile[...] = read_layer_block(self.path, self.layer, s, e)
+            return tile
+        bad = ctypes.c_int64(-1)
+        rc = self._hip.vcy_loom_block_host(self._calls, self._d, self.G, self.C, self.chunk[0], self.chunk[1], self.dtype.itemsize,
+                                           self.filters, s, e, tile.ctypes.data, e - s, self.threads, ctypes.byref(bad))
+        if rc != 0:
+            ncc = (e - 1) // self.chunk[1] - s // self.chunk[1] + 1
+            at = (bad.value // ncc * self.chunk[0], (s // self.chunk[1] + bad.value % ncc) * self.chunk[1])
+            what = {-4: "does not inflate to the chunk size", -5: "could not be read"}.get(rc, f"failed ({rc})")
+            raise IOError(f"{self.path}: layer {self.layer}: the chunk at (gene {at[0]}, cell {at[1]}) {what}")
+        return tile
+
+    def _work(self) -> None:
+        try:
+            for i, (s, e) in enumerate(self.blocks()):
+                k = i & 1
+                self._free[k].acquire()
+                if self._stop:
+                    return
+                if self._events[k] is not None:            # the caller's copy out of this buffer
+                    self._events[k].synchronize()
+                    self._events[k] = None
+                self._queue.put((k, s, e, self._fill(self._buffers[k], s, e)))
+            self._queue.put(None)
+        except BaseException as exc:                       # handed to the caller, raised from __next__
+            self._queue.put(exc)
+
+    def __iter__(self):
+        import queue
+        import threading
+        if self._thread is not None:
+            raise RuntimeError("a LayerBlockReader is iterated once")
+        self._queue = queue.Queue()
+        self._thread = threading.Thread(target=self._work, name="loom-block-reader", daemon=True)
+        self._thread.start()
+        return self
+
+    def pinned_tile(self):
+        """The tile handed out last as a flat page-locked torch.uint8 tensor (None when the buffers are plain host memory)."""
+        if self._held is None or not self._owners:
+            return None
+        return self._owners[self._held]
+
+    def copied(self, event) -> None:
+        """`event` (anything with synchronize()) is reached when the caller's copy of the tile handed out last is done."""
+        if self._held is not None:
+            self._events[self._held] = event
+
+    def __next__(self):
+        if self._queue is None:
+            iter(self)
+        if self._held is not None:                         # asking for block i + 1 hands the buffer of block i back: block i + 2 goes there,
+            self._free[self._held].release()               # after the event given to copied(), while block i + 1 (filled already) is worked on
+            self._held = None
+        item = self._queue.get()
+        if item is None:
+            self._queue.put(None)
+            raise StopIteration
+        if isinstance(item, BaseException):
+            self._queue.put(None)
+            raise item
+        self._held, s, e, tile = item
+        return s, e, tile
+
+    def close(self) -> None:
+        self._stop = True
+        if self._thread is not None:
+            for sem in self._free:
+                sem.release()
+            self._thread.join()
+            self._thread = None
+        self._buffers, self._owners = [], []
+        if self._d is not None:
+            self._L.H5Dclose(self._d)
+            self._d = None
+        if self._f is not None:
+            self._L.H5Fclose(self._f)
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_layer_csr(path: str, layer: str, cell_block: int = 8192, c0: int = 0, c1: Optional[int] = None, engine: str = "hyperslab",
+                   threads: Optional[int] = None):
     """A count layer of a .loom file straight into the device CSR form of the atlas path (ops.CsrCounts, cells-major): the
     file is read in blocks of `cell_block` cells (hyperslabs of the genes x cells dataset), each block is transposed and
     compacted on the device, so neither the host nor the device ever holds the dense layer (analysis.py:59-61 loads it
-    whole as float64).  c0:c1 restricts to a range of cells (a rank's shard)."""
+    whole as float64).  c0:c1 restricts to a range of cells (a rank's shard).
+
+    engine="stream" (opt-in) returns the same CsrCounts, bit for bit, by another route: a LayerBlockReader inflates the
+    block's chunks on `threads` host threads while the block before it is on the device, and the block goes up in the file's
+    element type to be validated, transposed and compacted by the vcy_loom_tile_* kernels (ops.csr_from_tiles)."""
     import torch
     from . import ops
+    if engine not in ("hyperslab", "stream"):
+        raise ValueError(f"engine must be 'hyperslab' or 'stream', got {engine!r}")
     dev = ops.require_gpu()
+    if engine == "stream":
+        with LayerBlockReader(path, layer, cell_block, c0, c1, threads) as reader:
+            if reader.dtype in ops.LOOM_ELEM and reader.G > 0:        # int8 / int16 / uint64 layers: the kernels do not take them
+                return ops.csr_from_tiles(reader)
     G, C = layer_shape(path, layer)
     c1 = C if c1 is None else c1
     ptr, idx, dat = [torch.zeros(1, dtype=torch.int64, device=dev)], [], []
@@ -319,13 +606,19 @@ def read_layer_csr(path: str, layer: str, cell_block: int = 8192, c0: int = 0, c
 
 
 def write_loom(path: str, layers: Dict[str, np.ndarray], col_attrs: Optional[Dict[str, np.ndarray]] = None,
-               row_attrs: Optional[Dict[str, np.ndarray]] = None, matrix: Optional[np.ndarray] = None) -> None:
+               row_attrs: Optional[Dict[str, np.ndarray]] = None, matrix: Optional[np.ndarray] = None,
+               chunks: Optional[Tuple[int, int]] = None, compression: Optional[int] = None, shuffle: bool = False) -> None:
     """Write the layout velocyto's counting pipeline produces (commands/_run.py:283-297): /matrix float32,
-    /layers/<name>, /row_attrs/<name>, /col_attrs/<name> (numeric or fixed-length string arrays)."""
+    /layers/<name>, /row_attrs/<name>, /col_attrs/<name> (numeric or fixed-length string arrays).
+    chunks=(genes, cells): /matrix and the layers are written chunked (the shape clipped to the dataset's), with gzip at level
+    `compression` if given and the byte shuffle in front of it if `shuffle` - what loompy writes ((64, 64), gzip 2).  The
+    defaults write contiguous datasets, as before."""
     L = _lib()
+    if chunks is None and (compression or shuffle):
+        raise ValueError("compression and shuffle need chunks=(genes, cells)")
     f = _check(L.H5Fcreate(path.encode(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT), f"create {path}")
 
-    def put(parent, name, arr):
+    def put(parent, name, arr, chunked=False):
         arr = np.asarray(arr)
         if arr.dtype.kind in ("U", "O"):
             arr = np.char.encode(arr.astype(str), "utf-8")
@@ -337,7 +630,18 @@ def write_loom(path: str, layers: Dict[str, np.ndarray], col_attrs: Optional[Dic
             L.H5Tset_size(tp, max(arr.dtype.itemsize, 1))
         else:
             tp = L._native[_NP2H5[arr.dtype]]
-        d = _check(L.H5Dcreate2(parent, name.encode(), tp, sp, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), f"create {name}")
+        dcpl = H5P_DEFAULT
+        if chunked and chunks is not None and arr.ndim == 2 and arr.size:
+            dcpl = _check(L.H5Pcreate(hid_t.in_dll(L, "H5P_CLS_DATASET_CREATE_ID_g").value), "H5Pcreate")
+            ch = (hsize_t * 2)(max(1, min(int(chunks[0]), arr.shape[0])), max(1, min(int(chunks[1]), arr.shape[1])))
+            _check(L.H5Pset_chunk(dcpl, 2, ch), "H5Pset_chunk")
+            if shuffle:
+                _check(L.H5Pset_shuffle(dcpl), "H5Pset_shuffle")
+            if compression:
+                _check(L.H5Pset_deflate(dcpl, min(int(compression), 9)), "H5Pset_deflate")
+        d = _check(L.H5Dcreate2(parent, name.encode(), tp, sp, H5P_DEFAULT, dcpl, H5P_DEFAULT), f"create {name}")
+        if dcpl != H5P_DEFAULT:
+            L.H5Pclose(dcpl)
         _check(L.H5Dwrite(d, tp, H5S_ALL, H5S_ALL, H5P_DEFAULT, arr.ctypes.data), f"write {name}")
         L.H5Dclose(d)
         L.H5Sclose(sp)
@@ -346,12 +650,12 @@ def write_loom(path: str, layers: Dict[str, np.ndarray], col_attrs: Optional[Dic
 
     try:
         first = next(iter(layers.values()))
-        put(f, "matrix", np.asarray(matrix if matrix is not None else sum(np.asarray(v, dtype=np.float32) for v in layers.values()), dtype=np.float32))
+        put(f, "matrix", np.asarray(matrix if matrix is not None else sum(np.asarray(v, dtype=np.float32) for v in layers.values()), dtype=np.float32), True)
         for grp, items in (("layers", layers), ("col_attrs", col_attrs or {"CellID": np.arange(first.shape[1])}),
                            ("row_attrs", row_attrs or {"Gene": np.arange(first.shape[0])})):
             g = _check(L.H5Gcreate2(f, grp.encode(), H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), f"create group {grp}")
             for k, v in items.items():
-                put(g, k, v)
+                put(g, k, v, grp == "layers")
             L.H5Gclose(g)
     finally:
         L.H5Fclose(f)

@@ -438,6 +438,110 @@ def csr_gene_stats(counts: CsrCounts, cell_mask=None) -> torch.Tensor:
     return out
 
 
+# --------------------------------------------------------------------------- .loom ingest in blocks of cells (csrc/ingest.hip)
+LOOM_ELEM = {np.dtype(k): v for k, v in (("uint8", 0), ("uint16", 1), ("uint32", 2), ("int32", 3), ("int64", 4), ("float32", 5), ("float64", 6))}
+LOOM_NOT_INTEGER = "layer {} holds non-integer values: not a count layer"
+LOOM_OUT_OF_RANGE = "layer {}: counts outside 0..65535 cannot be held as uint16"
+
+
+def loom_tile_workspace(G: int, B: int, dev) -> torch.Tensor:
+    return torch.empty(max(int(_lib.lib().vcy_loom_tile_workspace_bytes(G, B)) // 8, 1), dtype=torch.int64, device=dev)
+
+
+def _device_tiles(reader):
+    """The tiles of a loom_io.LayerBlockReader on the device, in the file's element type: yields (i, s, e, tile) with `tile` a flat
+    uint8 tensor holding the (G, e - s) block, ready on the current stream.  The upload runs on a side stream out of the reader's
+    page-locked buffer; the reader gets the copy's event (it overwrites the buffer after it), and two device buffers alternate so
+    that block i + 1 goes up while the kernels of block i run."""
+    dev = require_gpu()
+    main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    nbytes = max(reader.G * reader.width * reader.dtype.itemsize, 1)
+    dbuf = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+    done = [None, None]
+    side.wait_stream(main)
+    for i, (s, e, tile) in enumerate(reader):
+        k, n = i & 1, tile.nbytes
+        src = reader.pinned_tile()
+        src = src[:n] if src is not None else torch.from_numpy(tile.reshape(-1).view(np.uint8))
+        with torch.cuda.stream(side):
+            if done[k] is not None:
+                side.wait_event(done[k])                      # the kernels that read this buffer two blocks ago
+            dbuf[k][:n].copy_(src, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        reader.copied(ev)
+        main.wait_event(ev)
+        yield i, s, e, dbuf[k]
+        done[k] = torch.cuda.Event()
+        done[k].record(main)
+    main.wait_stream(side)
+
+
+def _raise_unless_counts(results: np.ndarray, layer: str) -> None:
+    """The ValueErrors of loom_io.read_layer_csr, block by block in its order: a non-integer block first, then its range."""
+    for nonint, neg, over, _ in results:
+        if nonint:
+            raise ValueError(LOOM_NOT_INTEGER.format(layer))
+        if neg or over:
+            raise ValueError(LOOM_OUT_OF_RANGE.format(layer))
+
+
+def csr_from_tiles(reader) -> CsrCounts:
+    """The CsrCounts of the cells a loom_io.LayerBlockReader walks - what loom_io.read_layer_csr(engine="hyperslab") returns for them,
+    bit for bit.  Per block: asynchronous upload of the page-locked tile in the file's element type, vcy_loom_tile_count, cumulative
+    sum, ONE host read (the block's total, to size its arrays), vcy_loom_tile_fill.  Validation costs no host read: every block
+    leaves its result block on the device and they are read together after the last one."""
+    L = _lib.lib()
+    dev = require_gpu()
+    G, elem, blocks = reader.G, LOOM_ELEM[reader.dtype], reader.blocks()
+    results = torch.zeros((max(len(blocks), 1), 4), dtype=torch.int64, device=dev)
+    ws = loom_tile_workspace(G, reader.width, dev)
+    ptr, idx, dat = [torch.zeros(1, dtype=torch.int64, device=dev)], [], []
+    base = 0
+    for i, s, e, tile in _device_tiles(reader):
+        B = e - s
+        nnz, sums = torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+        _lib.check(L.vcy_loom_tile_count(tile.data_ptr(), nnz.data_ptr(), sums.data_ptr(), results[i].data_ptr(), ws.data_ptr(), G, B, B, elem,
+                                         _stream()), "loom_tile_count")
+        row_start = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(nnz, 0, out=row_start[1:])
+        total = int(row_start[-1])
+        ii, dd = torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, dtype=torch.int16, device=dev)
+        if total:
+            _lib.check(L.vcy_loom_tile_fill(tile.data_ptr(), ws.data_ptr(), row_start.data_ptr(), ii.data_ptr(), dd.data_ptr(), total, G, B, B, elem,
+                                            _stream()), "loom_tile_fill")
+        ptr.append(base + row_start[1:])
+        base += total
+        idx.append(ii)
+        dat.append(dd)
+    res = results[: len(blocks)].cpu().numpy()
+    _raise_unless_counts(res, reader.layer)
+    cat = lambda xs, dt: torch.cat(xs) if xs else torch.empty(0, dtype=dt, device=dev)
+    data = cat(dat, torch.int16)
+    if not (len(res) and int(res[:, 3].max()) > 255):
+        data = data.to(torch.uint8)
+    return CsrCounts(torch.cat(ptr), cat(idx, torch.int32), data, G)
+
+
+def counts_from_tiles(reader) -> Tuple[CountMatrix, torch.Tensor, np.ndarray]:
+    """The cells a loom_io.LayerBlockReader walks as a resident uint16 CountMatrix (vcy_loom_tile_dense per block: validation,
+    conversion and transposition in one pass over the tile, no host read per block) -> (counts, per-cell sums as int64,
+    per-block result blocks (blocks, 4) on the host: non-integer, negative, above 65535, maximum).  The counts mean something only
+    when the three flags are clear everywhere."""
+    L = _lib.lib()
+    dev = require_gpu()
+    G, C, elem, blocks = reader.G, reader.c1 - reader.c0, LOOM_ELEM[reader.dtype], reader.blocks()
+    ld = padded_ld(G)
+    out = torch.empty((C, ld), dtype=torch.int16, device=dev)
+    sums = torch.zeros(C, dtype=torch.int64, device=dev)
+    results = torch.zeros((max(len(blocks), 1), 4), dtype=torch.int64, device=dev)
+    ws = loom_tile_workspace(ld, reader.width, dev)
+    for i, s, e, tile in _device_tiles(reader):
+        _lib.check(L.vcy_loom_tile_dense(tile.data_ptr(), out.data_ptr(), sums[s - reader.c0:].data_ptr(), results[i].data_ptr(), ws.data_ptr(),
+                                         G, e - s, e - s, elem, s - reader.c0, C, ld, _stream()), "loom_tile_dense")
+    return CountMatrix(out, G), sums, results[: len(blocks)].cpu().numpy()
+
+
 def transpose_csr(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, G: int, block_nnz: int = 1 << 25):
     """(indptr, indices, data) of a (C, G) CSR with sorted rows -> the same of its (G, C) transpose, rows sorted.  Index plumbing
     on whatever device the tensors live on, in blocks of whole rows holding about `block_nnz` stored elements (the sort
