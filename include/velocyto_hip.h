@@ -389,6 +389,34 @@ int vcy_gene_select_advance(void *state, void *hist, int pass, int ntargets, int
 int vcy_gene_select_finish(const void *state, const int *lo_target, const int *hi_target, const double *t_host, int nq, int ntargets,
                            double *out, int64_t G, int dtype, vcy_stream stream);
 
+/* The streamed select under a mask: the conditional percentiles of estimation.py:200-202, 222, 229-231, 255
+ * (y[x > percentile(x, 90)], y[x <= percentile(x, 1)]) and percentiles over a subset of the cells (steady_state_bool), from cell
+ * blocks, exact, memory O(genes).  The protocol is vcy_gene_select_*'s: vcy_gene_mselect_begin; per pass = 0 ..
+ * vcy_gene_select_passes(dtype) - 1, vcy_gene_mselect_count_block on EVERY block (any order, any blocking), then
+ * vcy_gene_mselect_advance; then vcy_gene_mselect_finish.  Two things differ.
+ * The mask: cell c counts for gene g iff (cell_mask == NULL or cell_mask[c] != 0; uint8 (C), device; a row it removes is not
+ * read) and (mask_mode 0, or mask_mode 1 and (double)mask_src[c,g] > mask_thr[g], or mask_mode 2 and (double)mask_src[c,g] <=
+ * mask_thr[g]): the comparison vcy_gene_quantiles makes, so a NaN threshold keeps nothing.  mask_src (C, ld) of dtype may be M
+ * itself, which is then read once; mask_thr (G) fp64.  Every pass must be given the same masks.
+ * The ranks: begin takes percentiles, not ranks, because a gene's population n_g - the number of its kept cells - depends on the
+ * data.  Pass 0 counts one histogram for all targets; its total per gene is n_g, and advance of pass 0 derives per gene and
+ * percentile h = (n_g - 1) * (q / 100), lo = floor(h), hi = min(lo + 1, n_g - 1), t = h - lo (vcy_gene_quantiles' arithmetic) and
+ * keeps both ranks and t in the state: no extra walk over the data.  Cell-sharded callers add the (G, 256) histogram of pass 0 -
+ * and all (2 nq, G, 256) of the later passes - as int32 before advance, so every rank derives the same n_g.
+ *   state: vcy_gene_mselect_state_bytes(G, nq) device bytes: (2 nq, G) uint64 prefixes, (nq, G) fp64 t, (G) int64 n_g, (2 nq, G)
+ *          uint32 ranks.   hist: vcy_gene_select_hist_bytes(G, 2 nq) device bytes.   nq <= 8.
+ * finish: out (nq, G) fp64 = numpy's _lerp of v[lo], v[hi] at t (at t == 0 it is v[lo]); NaN where n_g == 0.  counts (G) int64 =
+ * n_g, or NULL.  vcy_gene_quantiles stores masked-out entries as +inf and sorts them last, this select skips them: the two give
+ * the same bits on finite data (a kept +inf is where they could part).  Keys as vcy_gene_select_*: -0.0 below +0.0, a NaN among
+ * the kept values is not ordered.  At most 2^31 - 1 cells over all blocks and ranks (32-bit counts), C <= 2^31 - 1 per call. */
+size_t vcy_gene_mselect_state_bytes(int64_t G, int nq);
+int vcy_gene_mselect_begin(void *state, void *hist, const double *qs_host, int nq, int64_t G, int dtype, vcy_stream stream);
+int vcy_gene_mselect_count_block(const void *M, const void *mask_src, const double *mask_thr, int mask_mode,
+                                 const unsigned char *cell_mask, const void *state, void *hist, int pass, int nq, int64_t C,
+                                 int64_t G, int64_t ld, int dtype, vcy_stream stream);
+int vcy_gene_mselect_advance(void *state, void *hist, int pass, int nq, int64_t G, int dtype, vcy_stream stream);
+int vcy_gene_mselect_finish(const void *state, int nq, double *out, int64_t *counts, int64_t G, int dtype, vcy_stream stream);
+
 /* estimation.fit_slope_weighted_offset / fit_slope_weighted / fit_slope_offset with the
  * binary or dense weights of VelocytoLoom.fit_gammas (estimation.py:191-264, 300-366;
  * analysis.py:1179-1257), solved exactly: weighted moments per gene in one pass, then the
@@ -415,6 +443,14 @@ int vcy_fit_weighted(const void *Y, const void *X, int weight_mode, const void *
 int vcy_fit_weighted_moments(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
                              const double *scale_a, const double *scale_b, const double *down, const double *up, double *moments,
                              void *workspace, int64_t C, int64_t G, int64_t ld, int dtype, vcy_stream stream);
+/* vcy_fit_weighted_moments over the cells with cell_mask[c] != 0 (uint8 (C), device, not NULL): the steady-state cells of
+ * fit_gammas without a gathered copy of the block.  A masked-out row adds nothing and is not read; the kept cells are summed in
+ * the same fixed block order, so an all-ones mask gives vcy_fit_weighted_moments' moments bit for bit.  n_cells of the solve
+ * is then the number of kept cells.                                                                                          */
+int vcy_fit_weighted_moments_masked(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
+                                    const double *scale_a, const double *scale_b, const double *down, const double *up,
+                                    const unsigned char *cell_mask, double *moments, void *workspace, int64_t C, int64_t G,
+                                    int64_t ld, int dtype, vcy_stream stream);
 int vcy_fit_weighted_from_moments(const double *moments, int64_t n_cells, int fit_offset, int box_q, double lo_gamma,
                                   double up_gamma_default, const double *up_gamma, const double *q_fixed, float *gamma, float *q,
                                   float *R2, int64_t G, vcy_stream stream);

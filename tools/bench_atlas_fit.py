@@ -8,7 +8,13 @@ count: vcy_gene_select_count_block alone on a resident block of G genes, f32 and
        element size; the rate is held against STREAM_TBS, the read rate the project measured for its streaming stage B
        (profiles/r06_pool_levers.txt: 24 GB at 6.2 TB/s).
 path:  AtlasPath.run(timed=True) with fit="maxmin_diag" and fit="slope" ALTERNATING in one process on the same data: wall time
-       per run between device synchronisations and the stage times (stage B holds all the extra walks, re-pooling included)."""
+       per run between device synchronisations and the stage times (stage B holds all the extra walks, re-pooling included).
+Opt-in parts (not in the default PART):
+mcount:  the masked counting launch (vcy_gene_mselect_count_block) against the unmasked one on a resident block of MC_CELLS (100 000)
+         cells, per digit, f32 and f64, two targets each (percentile 10): no value mask, the mask's source = the matrix itself, and
+         a second matrix; with and without a cell mask that keeps half of the rows.
+options: stage B of AtlasPath.run(timed=True) with each of fit_gammas' options against the default fit, ONE object whose options are
+         switched between runs, alternating, at the first of SIZES."""
 import json
 import os
 import sys
@@ -130,6 +136,95 @@ def part_path(spec):
     torch.cuda.empty_cache()
 
 
+def part_mcount():
+    C = int(os.environ.get("MC_CELLS", 100_000))
+    say(f"## the masked counting launch (vcy_gene_mselect_count_block) against the unmasked one, resident block of {C} cells, percentile 10 "
+        "(two targets), median of 5 (min .. max); the value mask keeps x > 4.5, about a tenth of the entries")
+    L = _lib.lib()
+    for dt in (torch.float32, torch.float64):
+        es = 4 if dt == torch.float32 else 8
+        ld = ops.padded_ld(G)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        mats = []
+        for _ in range(2):
+            t = torch.empty((C, ld), dtype=dt, device=dev)
+            for a in range(0, C, 50_000):
+                b = min(C, a + 50_000)
+                t[a:b] = (torch.rand((b - a, ld), generator=gen, device=dev) ** 2 * 8 * (torch.rand((b - a, ld), generator=gen, device=dev) < 0.4)).to(dt)
+            mats.append(ops.CellMatrix(t, G))
+        M, S = mats
+        thr = torch.full((G,), 4.5, dtype=torch.float64, device=dev)
+        half = (torch.arange(C, device=dev) % 2 == 0).to(torch.uint8)
+        gb = C * ld * es / 1e9
+        plain = ops.StreamedGeneQuantiles(G, [10], C, dt)
+        # (label, mask_src, mask_mode, cell mask, bytes read relative to the block)
+        variants = [("masked, no value mask", None, 0, None, 1.0), ("masked, source = M", M, 1, None, 1.0), ("masked, second matrix", S, 1, None, 2.0),
+                    ("no value mask, half the rows", None, 0, half, 0.5), ("second matrix, half the rows", S, 1, half, 1.0)]
+        sels = [ops.StreamedMaskedGeneQuantiles(G, [10], dt) for _ in variants]
+        st = lambda: torch.cuda.current_stream().cuda_stream
+        for p_no in range(plain.passes):
+            def unmasked():
+                _lib.check(L.vcy_gene_select_count_block(M.t.data_ptr(), None, None, None, plain.state.data_ptr(), plain.hist.data_ptr(), plain.pass_no,
+                                                         plain.nt, C, G, ld, plain.code, st()), "count_block")
+            base, lo, hi = timed(unmasked)
+            say(f"{str(dt):14s} digit {p_no}: unmasked{'':30s} {base:7.3f} ms ({lo:.3f} .. {hi:.3f})  reads {gb:.1f} GB -> {gb / base:.2f} TB/s")
+            plain.hist.zero_(); plain.add_block(M); plain.advance()
+            for (label, src, mode, cm, rel), sel in zip(variants, sels):
+                def masked():
+                    _lib.check(L.vcy_gene_mselect_count_block(M.t.data_ptr(), None if src is None else src.t.data_ptr(), thr.data_ptr() if mode else None,
+                                                              mode, None if cm is None else cm.data_ptr(), sel.state.data_ptr(), sel.hist.data_ptr(),
+                                                              sel.pass_no, sel.nq, C, G, ld, sel.code, st()), "mselect_count_block")
+                med, lo, hi = timed(masked)
+                say(f"{str(dt):14s} digit {p_no}: {label:38s} {med:7.3f} ms ({lo:.3f} .. {hi:.3f})  reads {gb * rel:.1f} GB -> {gb * rel / med:.2f} TB/s  "
+                    f"= x{med / base:.2f} of the unmasked launch ({med - base:+.3f} ms)")
+                sel.hist.zero_(); sel.add_block(M, src, thr if mode else None, mode, cm); sel.advance()
+        del mats, M, S, sels, plain
+        torch.cuda.empty_cache()
+    say()
+
+
+def part_options(spec):
+    c, b = spec.split("x")
+    C = int(c)
+    block = C // int(b)
+    cS, cU, totS, totU, pcs, emb = atlas.synth_atlas(C, G, 30, dev, density=0.08)
+    fS, fU = atlas.size_factors(totS, totU, C)
+    path = atlas.AtlasPath(cS, cU, fS, fU, pcs, emb, k=30, n_neighbors=500, sampled_fraction=0.5, block_cells=block, fit="maxmin_diag")
+    rows = {"default": dict(fit_offset=True, fixperc_q=False, limit_gamma=False, ss=False),
+            "limit_gamma": dict(fit_offset=True, fixperc_q=False, limit_gamma=True, ss=False),
+            "fit_offset=False, fixperc_q": dict(fit_offset=False, fixperc_q=True, limit_gamma=False, ss=False),
+            "fit_offset=False, limit_gamma": dict(fit_offset=False, fixperc_q=False, limit_gamma=True, ss=False),
+            "fit_offset=False": dict(fit_offset=False, fixperc_q=False, limit_gamma=False, ss=False),
+            "steady state (half the cells)": dict(fit_offset=True, fixperc_q=False, limit_gamma=False, ss=True),
+            "steady state, limit_gamma": dict(fit_offset=True, fixperc_q=False, limit_gamma=True, ss=True)}
+    half = (torch.arange(C, device=dev) % 2 == 0).to(torch.uint8)
+    say(f"## stage B of AtlasPath.run(timed=True) per fit option, {C} cells x {G} genes, f32, {len(path.blocks())} block(s) of {path.block_cells} cells; "
+        f"ONE object, options switched between runs, alternating, {STEPS} timed runs each after one warm-up each")
+
+    def set_row(o):
+        path.fit_offset, path.fixperc_q, path.limit_gamma = o["fit_offset"], o["fixperc_q"], o["limit_gamma"]
+        path._ss, path.n_fit_cells = (half, int(half.sum())) if o["ss"] else (None, C)
+    tb, peak = {n: [] for n in rows}, {}
+    for n, o in rows.items():
+        set_row(o)
+        path.run(); torch.cuda.synchronize()
+    for _ in range(STEPS):
+        for n, o in rows.items():
+            set_row(o)
+            before = path.stage_ms.copy()
+            path.run(timed=True)
+            torch.cuda.synchronize()
+            tb[n].append((path.stage_ms - before)[1])
+            peak[n] = path.select_state_bytes
+    base = float(np.median(tb["default"]))
+    for n in rows:
+        m = float(np.median(tb[n]))
+        say(f"{n:32s} stage B {m:8.1f} ms ({min(tb[n]):.1f} .. {max(tb[n]):.1f})  = default {m - base:+.1f} ms (x{m / base:.3f})   select state {peak[n] / 1e6:.0f} MB")
+    say()
+    del path, cS, cU
+    torch.cuda.empty_cache()
+
+
 say(f"# tools/bench_atlas_fit.py  {time.strftime('%Y-%m-%d %H:%M:%S')}  device {torch.cuda.get_device_name(0)}  digit bits {_lib.lib().vcy_gene_select_digit_bits()}")
 say("smi before: " + json.dumps(smi_sample()))
 if "count" in PARTS:
@@ -137,5 +232,9 @@ if "count" in PARTS:
 if "path" in PARTS:
     for spec in SIZES:
         part_path(spec)
+if "mcount" in PARTS:
+    part_mcount()
+if "options" in PARTS:
+    part_options(SIZES[0])
 say("smi after: " + json.dumps(smi_sample()))
 out_fh.close()

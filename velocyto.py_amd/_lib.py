@@ -134,6 +134,11 @@ SIGNATURES = {
     "vcy_gene_select_advance": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp]),
     "vcy_gene_select_finish": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), c_int, c_int, c_vp, c_i64,
                                        c_int, c_vp]),
+    "vcy_gene_mselect_state_bytes": (c_sz, [c_i64, c_int]),
+    "vcy_gene_mselect_begin": (c_int, [c_vp, c_vp, ctypes.POINTER(c_dbl), c_int, c_i64, c_int, c_vp]),
+    "vcy_gene_mselect_count_block": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_gene_mselect_advance": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp]),
+    "vcy_gene_mselect_finish": (c_int, [c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),
     "vcy_gamma_weights": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_dbl, c_int, c_vp]),
     "vcy_prepare_markov": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_dbl, c_dbl, c_int, c_vp]),
     "vcy_row_sums": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
@@ -153,6 +158,8 @@ SIGNATURES = {
     "vcy_fit_weighted": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_dbl,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     "vcy_fit_weighted_moments": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "vcy_fit_weighted_moments_masked": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                                c_int, c_vp]),
     "vcy_fit_weighted_from_moments": (c_int, [c_vp, c_i64, c_int, c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "vcy_gene_slices_pack": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     "vcy_gene_slices_unpack": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),

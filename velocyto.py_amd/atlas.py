@@ -15,6 +15,8 @@ same kernels as the resident path (bench.py `Pipeline`); what changes is where t
   B        fit_slope moments of the rank's own cells, summed over blocks, all-reduced (3 G doubles).  AtlasPath(fit="maxmin_diag"):
            velocyto's default weighted fit instead - its per-gene percentiles from an exact select streamed over the blocks
            (ops.StreamedGeneQuantiles: integer histograms, all-reduced), then the weighted moments (10 G doubles) and the boxed solve.
+           fit_gammas' fit_offset / fixperc_q / limit_gamma / steady_state_bool ride on the same walks: their conditional percentiles
+           from the masked select (ops.StreamedMaskedGeneQuantiles), the moments over the steady-state cells.
   C + D    per block: e rows = [block | sampled neighbours outside the block], pooled on the spot when the matrices are not
            resident; vcy_coldeltacor_partial_fused on the block with renumbered neighbour lists.
 
@@ -85,11 +87,21 @@ class AtlasPath:
                  sampling_probs=(0.5, 0.1), block_cells: int = 0, dtype=torch.float32, psc: float = 1e-10, seed: int = 15071990,
                  knn: str = "auto", fit: str = "slope", shift: bool = False, sigma_corr: float = 0.05, expression_scaling: bool = True,
                  scaling_penalty: float = 1.0, balanced: bool = False, b_sight: Optional[int] = None, b_maxl: Optional[int] = None,
-                 group_constraint=None):
+                 group_constraint=None, fit_offset: bool = True, fixperc_q: bool = False, limit_gamma: bool = False, steady_state_bool=None):
         """fit: how stage B fits gamma.  "slope" (the default): gamma = max(0, sum xy / sum xx), unweighted, no offset (fit_slope,
         estimation.py:267-279).  "maxmin_diag" (or "default"): velocyto's default fit_gammas(weights="maxmin_diag", fit_offset=True)
         (analysis.py:1179-1257), the recipe of VelocytoLoom.fit_gammas and ShardedLoom.fit_gammas, with the per-gene percentiles
         taken by a streamed exact select (ops.StreamedGeneQuantiles): 9 walks over the pooled blocks in f32, 17 in f64.
+        fit_offset, fixperc_q, limit_gamma, steady_state_bool (fit="maxmin_diag" only; anything but the defaults with fit="slope" is a
+        ValueError): VelocytoLoom.fit_gammas' options of these names with weighted=True, weights="maxmin_diag" (analysis.py:1120-1260).
+        fit_offset=True: the box fit, with up_gamma = estimation._median_and_up_gamma when limit_gamma (fixperc_q is ignored);
+        fit_offset=False, fixperc_q=True: the offset fixed to estimation._fixperc_q, gamma in [0, 20] (limit_gamma is ignored);
+        fit_offset=False, fixperc_q=False: no offset, gamma in [1e-8, up_gamma] with limit_gamma, else in [0, 20].
+        steady_state_bool: a bool mask over the rank's own cells or over all C cells (None or all-true: all cells).  As in the facade
+        the weights' thresholds are taken over all cells; the limit_gamma / fixperc_q percentiles and the moments over the masked
+        cells only.  Their conditional percentiles come from the masked streamed select (ops.StreamedMaskedGeneQuantiles) in the
+        walks the default fit already makes: the number of walks does not change.  With none of the four given the run is bit for
+        bit the default fit's.
         shift: also calculate_embedding_shift (analysis.py:1670-1733, stage E) with sigma_corr, expression_scaling and scaling_penalty
         as there, block by block while the block is in the staging buffers: run() then leaves tp, delta_embedding, scaling and
         delta_embedding_unscaled of the rank's own cells (see _stage_e); delta_S is never formed.
@@ -102,6 +114,10 @@ class AtlasPath:
         if fit not in ("slope", "maxmin_diag", "default"):
             raise ValueError(f"AtlasPath: unknown fit={fit!r} (\"slope\", \"maxmin_diag\" or \"default\")")
         self.fit = "slope" if fit == "slope" else "maxmin_diag"
+        self.fit_offset, self.fixperc_q, self.limit_gamma = bool(fit_offset), bool(fixperc_q), bool(limit_gamma)
+        if self.fit == "slope" and (not self.fit_offset or self.fixperc_q or self.limit_gamma or steady_state_bool is not None):
+            raise ValueError("AtlasPath: fit_offset, fixperc_q, limit_gamma and steady_state_bool belong to fit=\"maxmin_diag\"; "
+                             "fit=\"slope\" has no offset, no weights and no steady-state cells")
         self.dev = dev = cS.indptr.device
         self.knn_mode = knn
         self.dtype = ops.resolve_dtype(dtype)
@@ -168,9 +184,13 @@ class AtlasPath:
         self.corr = torch.empty((self.nloc, self.nrndm), dtype=self.dtype, device=dev)
         self.gamma = None
         self.q = self.R2 = None            # fit="maxmin_diag": the offset and the weighted R2 of the fit (float32, like gamma)
-        self.fit_thresholds = None         # ... and its per-gene float64 thresholds {"denom_S", "denom_U", "down", "up"}
+        self.fit_thresholds = None         # ... and its per-gene float64 thresholds {"denom_S", "denom_U", "down", "up"}; with
+        #     limit_gamma also {"med_S", "p90_S", "med_U", "U_p10_above", "S_med_above", "n_above" (int64: cells with Sx > p90_S),
+        #     "up_gamma"}, with fixperc_q {"p1_S", "n_below" (int64: cells with Sx <= p1_S), "q_fixed"} - over the steady-state cells
         self.fit_moments = None            # ... and the all-reduced (10, G) moments they were solved from
         self.select_state_bytes = 0        # ... and the bytes the streamed select held at its peak
+        self._ss, self.n_fit_cells = self._steady_state(steady_state_bool)      # uint8 (nloc) or None = all cells; the cells the fit is over
+        self._blk = (0, self.nloc)         # the rows of the block _data_pass handed out last
         self._in_buf = None                # the block whose own rows the staging buffers hold
         self.stage_ms = np.zeros(4)
         self.stage_e_ms = 0.0              # shift=True, run(timed=True): milliseconds of stage E (kept out of stage_ms)
@@ -185,6 +205,21 @@ class AtlasPath:
         self._resident = None
         self._plan = None
         self.peak_block_bytes = 0
+
+    def _steady_state(self, ss) -> Tuple[Optional[torch.Tensor], int]:
+        """steady_state_bool as (the uint8 mask of the rank's own cells or None for all cells, the number of masked cells of all ranks)."""
+        if ss is None:
+            return None, self.C
+        m = torch.as_tensor(np.asarray(ss))
+        if m.dtype != torch.bool or m.ndim != 1 or m.numel() not in (self.nloc, self.C):
+            raise ValueError(f"AtlasPath: steady_state_bool must be a 1-d bool mask over the rank's own {self.nloc} cells or over all {self.C} cells")
+        if m.numel() != self.nloc:
+            m = m[self.c0:self.c1]
+        m = m.to(self.dev)
+        n = int(D.all_reduce_sum(m.sum().reshape(1).to(torch.int64)).item())
+        if n == 0:
+            raise ValueError("AtlasPath: steady_state_bool selects no cell")
+        return (None if n == self.C else m.to(torch.uint8).contiguous()), n
 
     def _knn(self, pcs_full: torch.Tensor):
         """Exact kNN of the own cells among all cells: brute force up to PRUNE_FROM cells, projection-pruned beyond (the
@@ -303,6 +338,7 @@ class AtlasPath:
             nb = b1 - b0
             ev[0].record()
             Sx_b, Ux_b = self._ebuf.rows(0, nb), self._ubuf.rows(0, nb)
+            self._blk = (b0, b1)
             if self._in_buf != bi:
                 self._pool(self.cS, self.fS, slice(b0, b1), Sx_b)
                 self._pool(self.cU, self.fU, slice(b0, b1), Ux_b)
@@ -318,12 +354,21 @@ class AtlasPath:
         """fit_gammas(weights="maxmin_diag", fit_offset=True) (analysis.py:1179-1257) over blocks, in three phases of walks:
         (1) percentiles [99.9, 100] of Sx and of Ux -> the denominators of VelocytoLoom._maxnorm_denominator; (2) percentiles
         [2, 98] of Sx/dS + Ux/dU -> the binary weights' thresholds; (3) the weighted moments, all-reduced and solved in the box
-        (the recipe of ShardedLoom.fit_gammas).  Phases 1 and 2 take one walk per 8-bit digit of the key each."""
+        (the recipe of ShardedLoom.fit_gammas).  Phases 1 and 2 take one walk per 8-bit digit of the key each.
+        limit_gamma / fixperc_q ride on the same walks (masked selects over the steady-state cells): the unconditional percentiles
+        ([50, 90] or [1] of Sx, [50] of Ux) in phase 1, the conditional ones, which need only those, in phase 2 beside [2, 98]."""
         G, C = self.G, self.C
         facts = {"abs_st": None, "absmax": None}
         selS = ops.StreamedGeneQuantiles(G, [99.9, 100], C, self.dtype, self.dev)
         selU = ops.StreamedGeneQuantiles(G, [99.9, 100], C, self.dtype, self.dev)
-        self.select_state_bytes = selS.state_bytes + selU.state_bytes
+        need_up = self.limit_gamma and (self.fit_offset or not self.fixperc_q)
+        need_qf = self.fixperc_q and not self.fit_offset
+        cmask = lambda: None if self._ss is None else self._ss[self._blk[0]:self._blk[1]]      # of the block being used
+        msel = lambda qs: ops.StreamedMaskedGeneQuantiles(G, qs, self.dtype, self.dev)
+        xS = msel([50, 90]) if need_up else (msel([1]) if need_qf else None)                  # phase 1 extras: of Sx ...
+        xU = msel([50]) if need_up else None                                                   # ... and of Ux
+        extra = [x for x in (xS, xU) if x is not None]
+        self.select_state_bytes = selS.state_bytes + selU.state_bytes + sum(x.state_bytes for x in extra)
         n_passes = 2 * selS.passes + 1
         i_pass = 0
 
@@ -342,42 +387,80 @@ class AtlasPath:
             def use(Sx_b, Ux_b):
                 selS.add_block(Sx_b)
                 selU.add_block(Ux_b)
+                if xS is not None:
+                    xS.add_block(Sx_b, cell_mask=cmask())
+                if xU is not None:
+                    xU.add_block(Ux_b, cell_mask=cmask())
                 if first:
                     self._gather_facts(Sx_b, facts)
             self._data_pass(i_pass, n_passes, use, ev, timed, tms)
             if first:
                 self._decide_rules(facts)
-            end_pass(selS, selU)
+            end_pass(selS, selU, *extra)
             i_pass += 1
         ev[0].record()
         denom = lambda p: torch.where(p[0] == 0, torch.clamp(p[1], min=0.001), p[0]).contiguous()     # _maxnorm_denominator's rule
         dS, dU = denom(selS.result()), denom(selU.result())
         del selS, selU
         selZ = ops.StreamedGeneQuantiles(G, [2, 98], C, self.dtype, self.dev, two=True)
-        self.select_state_bytes = max(self.select_state_bytes, selZ.state_bytes)
+        opt = {}                           # what limit_gamma / fixperc_q add to fit_thresholds
+        cond = []                          # phase 2 extras: (select, its matrix is Ux (else Sx), threshold, mask_mode)
+        if need_up:
+            qx = xS.result()
+            opt.update(med_S=qx[0].contiguous(), p90_S=qx[1].contiguous(), med_U=xU.result()[0].contiguous())
+            cond = [(msel([10]), True, opt["p90_S"], 1), (msel([50]), False, opt["p90_S"], 1)]     # y[x > p90] at 10, x[x > p90] at 50
+        elif need_qf:
+            opt.update(p1_S=xS.result()[0].contiguous())
+            cond = [(msel([50]), True, opt["p1_S"], 2)]                                           # y[x <= p1] at 50
+        del xS, xU, extra
+        self.select_state_bytes = max(self.select_state_bytes, selZ.state_bytes + sum(c[0].state_bytes for c in cond))
         ev[1].record()
         if timed:
             torch.cuda.synchronize()
             tms[1] += ev[0].elapsed_time(ev[1])
+
+        def use_z(Sx_b, Ux_b):
+            selZ.add_block(Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU)
+            for sel, of_u, thr, mode in cond:
+                sel.add_block(Ux_b if of_u else Sx_b, mask_src=Sx_b, mask_thr=thr, mask_mode=mode, cell_mask=cmask())
         while not selZ.done:
-            self._data_pass(i_pass, n_passes, lambda Sx_b, Ux_b: selZ.add_block(Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU), ev, timed, tms)
-            end_pass(selZ)
+            self._data_pass(i_pass, n_passes, use_z, ev, timed, tms)
+            end_pass(selZ, *[c[0] for c in cond])
             i_pass += 1
         th = selZ.result()
         down, up = th[0].contiguous(), th[1].contiguous()
         del selZ
         self.fit_thresholds = {"denom_S": dS, "denom_U": dU, "down": down, "up": up}
+        up_gamma = q_fixed = None
+        if need_up:                        # estimation._median_and_up_gamma from the streamed percentiles
+            y10, xm = cond[0][0].result()[0], cond[1][0].result()[0]
+            upg = torch.maximum(torch.full_like(y10, 1.5), y10 / xm)
+            up_gamma = torch.where(opt["med_U"] > opt["med_S"], upg, torch.full_like(upg, 1.5))
+            opt.update(U_p10_above=y10, S_med_above=xm, n_above=cond[0][0].counts(), up_gamma=up_gamma)
+        elif need_qf:                      # estimation._fixperc_q
+            q_fixed = cond[0][0].result()[0]
+            opt.update(n_below=cond[0][0].counts(), q_fixed=q_fixed)
+        self.fit_thresholds.update(opt)
+        del cond
         moms = []
 
         def use(Sx_b, Ux_b):
-            m = ops.fit_weighted_moments(Ux_b, Sx_b, 1, M=Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU, down=down, up=up)
+            m = ops.fit_weighted_moments(Ux_b, Sx_b, 1, M=Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU, down=down, up=up, cell_mask=cmask())
             moms[:] = [m if not moms else moms[0].add_(m)]
         self._data_pass(i_pass, n_passes, use, ev, timed, tms)
         ev[0].record()
         mom = moms[0] if moms else torch.zeros((10, G), dtype=torch.float64, device=self.dev)
         D.all_reduce_sum(mom)
         self.fit_moments = mom
-        gamma, q, R2 = ops.fit_weighted_from_moments(mom, C, fit_offset=True, box_q=True, lo_gamma=1e-8, up_gamma_default=20.0)
+        n = self.n_fit_cells
+        if self.fit_offset:                # the arguments of estimation._weighted_offset_device / VelocytoLoom.fit_gammas per branch
+            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=True, box_q=True, lo_gamma=1e-8, up_gamma_default=20.0, up_gamma=up_gamma)
+        elif need_qf:
+            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=False, lo_gamma=0.0, up_gamma_default=20.0, q_fixed=q_fixed)
+        elif need_up:
+            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=False, lo_gamma=1e-8, up_gamma=up_gamma)
+        else:
+            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=False, lo_gamma=0.0, up_gamma_default=20.0)
         gamma = torch.where(torch.isfinite(gamma), gamma, torch.zeros_like(gamma))                    # analysis.py:1260
         self.q, self.R2 = q, R2
         ev[1].record()
@@ -522,14 +605,22 @@ def grid_arrows(embedding, delta_embedding, smooth: float = 0.5, steps: Tuple = 
 
 
 def memory_plan(C: int, G: int, nnz_per_cell: float, world: int, block_cells: int, nrndm: int = 250, k: int = 30, count_bytes: int = 1,
-                elem_bytes: int = 4, halo_e: float = 0.1, halo_k: float = 0.25, fit: str = "slope", b_sight: int = 0) -> Dict[str, float]:
+                elem_bytes: int = 4, halo_e: float = 0.1, halo_k: float = 0.25, fit: str = "slope", b_sight: int = 0, fit_offset: bool = True,
+                fixperc_q: bool = False, limit_gamma: bool = False) -> Dict[str, float]:
     """Bytes one rank holds (GB).  halo_e / halo_k: E and count-row halos as fractions of the rank's own cells (measured:
     tools/halo_fraction.py, AtlasPath.n_e_halo / n_count_halo).  fit="maxmin_diag" adds the state of the streamed select at its
     peak (phase 1: three ranks - both of percentile 99.9 and the maximum - of Sx and of Ux): per (rank, gene) a 256-bin uint32
-    histogram, an 8-byte key prefix and a 4-byte rank; it does not grow with the cell count.  b_sight > 0 (AtlasPath(balanced=True)) adds
+    histogram, an 8-byte key prefix and a 4-byte rank; it does not grow with the cell count.  fit_offset / fixperc_q / limit_gamma
+    (AtlasPath's) add the masked selects that share phase 1: percentiles [50, 90] of Sx and [50] of Ux with limit_gamma, [1] of Sx
+    with fixperc_q - two such ranks per percentile, plus 8 bytes of fraction per percentile and 8 of population.  b_sight > 0 (AtlasPath(balanced=True)) adds
     the gathered int32 sight lists of ALL cells, C x (b_sight + 1) x 4 bytes, held while the graph is balanced."""
     lists = C * (b_sight + 1) * 4 if b_sight > 0 else 0
     select = 0 if fit == "slope" else 2 * 3 * G * (256 * 4 + 8 + 4)
+    msel = lambda nq: G * (2 * nq * (256 * 4 + 8 + 4) + nq * 8 + 8)
+    if fit != "slope" and limit_gamma and (fit_offset or not fixperc_q):
+        select += msel(2) + msel(1)
+    elif fit != "slope" and fixperc_q and not fit_offset:
+        select += msel(1)
     nloc = math.ceil(C / world)
     ld = ops.padded_ld(G)
     blk = min(block_cells if block_cells > 0 else nloc, nloc)

@@ -108,12 +108,15 @@ template <typename T> __device__ __forceinline__ T zvalue(T m, T m2, T a, T b, b
     return two ? (m / a + m2 / b) : m;   // true divisions, like Sx/denom_Sx + Ux/denom_Ux
 }
 
-template <typename T, int WMODE>
-__global__ __launch_bounds__(256) void k_moments_weighted(const T *__restrict__ Y, const T *__restrict__ X, const T *__restrict__ W,
-                                                           const T *__restrict__ M, const T *__restrict__ M2,
-                                                           const double *__restrict__ scale_a, const double *__restrict__ scale_b,
-                                                           const double *__restrict__ down, const double *__restrict__ up,
-                                                           double *__restrict__ part, int C, int G, int64_t ld)
+// CM: cells with cmask[c] == 0 add nothing and are not read (the steady-state cells of fit_gammas); the kept cells are summed in
+// the order the unmasked kernel sums them, so an all-ones mask gives its moments bit for bit.
+template <typename T, int WMODE, bool CM>
+__device__ __forceinline__ void moments_weighted_body(const T *__restrict__ Y, const T *__restrict__ X, const T *__restrict__ W,
+                                                      const T *__restrict__ M, const T *__restrict__ M2,
+                                                      const double *__restrict__ scale_a, const double *__restrict__ scale_b,
+                                                      const double *__restrict__ down, const double *__restrict__ up,
+                                                      double *__restrict__ part, int C, int G, int64_t ld,
+                                                      const unsigned char *__restrict__ cmask)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;   // lane <-> gene: coalesced 4/8-byte row segments
     if (g >= G) return;
@@ -130,6 +133,7 @@ __global__ __launch_bounds__(256) void k_moments_weighted(const T *__restrict__ 
     double sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0, sw = 0, swx = 0, swy = 0, swxx = 0, swxy = 0;
 #pragma unroll 4
     for (int c = c0; c < c1; ++c) {
+        if (CM && cmask[c] == 0) continue;   // the same for every lane: the row is skipped whole
         const int64_t o = (int64_t)c * ld + g;
         const double x = X[o], y = Y[o];
         double w;
@@ -146,6 +150,27 @@ __global__ __launch_bounds__(256) void k_moments_weighted(const T *__restrict__ 
     const int64_t s = G;
     p[0] = sx; p[s] = sy; p[2 * s] = sxx; p[3 * s] = sxy; p[4 * s] = syy;
     p[5 * s] = sw; p[6 * s] = swx; p[7 * s] = swy; p[8 * s] = swxx; p[9 * s] = swxy;
+}
+
+template <typename T, int WMODE>
+__global__ __launch_bounds__(256) void k_moments_weighted(const T *__restrict__ Y, const T *__restrict__ X, const T *__restrict__ W,
+                                                           const T *__restrict__ M, const T *__restrict__ M2,
+                                                           const double *__restrict__ scale_a, const double *__restrict__ scale_b,
+                                                           const double *__restrict__ down, const double *__restrict__ up,
+                                                           double *__restrict__ part, int C, int G, int64_t ld)
+{
+    moments_weighted_body<T, WMODE, false>(Y, X, W, M, M2, scale_a, scale_b, down, up, part, C, G, ld, nullptr);
+}
+
+template <typename T, int WMODE>
+__global__ __launch_bounds__(256) void k_moments_weighted_masked(const T *__restrict__ Y, const T *__restrict__ X, const T *__restrict__ W,
+                                                                  const T *__restrict__ M, const T *__restrict__ M2,
+                                                                  const double *__restrict__ scale_a, const double *__restrict__ scale_b,
+                                                                  const double *__restrict__ down, const double *__restrict__ up,
+                                                                  double *__restrict__ part, int C, int G, int64_t ld,
+                                                                  const unsigned char *__restrict__ cmask)
+{
+    moments_weighted_body<T, WMODE, true>(Y, X, W, M, M2, scale_a, scale_b, down, up, part, C, G, ld, cmask);
 }
 
 // Exact minimiser of  sum w (x m + q - y)^2  over [lo_m,hi_m] x [lo_q,hi_q] from the weighted
@@ -607,12 +632,21 @@ __global__ __launch_bounds__(1024) void k_gene_quantiles_reg(const T *__restrict
 constexpr int SEL_GENES = 64, SEL_GSTRIDE = 65, SEL_WAVES = 16, SEL_MAXT = 4, SEL_MAXCELLS = 32768, SEL_MAXTARGETS = 16;
 constexpr size_t SEL_LDS_PER_TARGET = (size_t)128 * SEL_GSTRIDE * sizeof(unsigned);
 
-template <typename T, int NT, bool TWO>
+//
+// MK (the masked select, vcy_gene_mselect_*): which cells count for a gene.  0: all (the instances of vcy_gene_select_*, whose
+// code the parameter leaves as it was).  1: the cells with cell_mask[c] != 0 (NULL = all).  2 and 3: of those, the cells with
+// v > mask_thr[g] (mask_mode 1) or v <= mask_thr[g] (mask_mode 2), compared in fp64 as k_build_z compares - a NaN threshold keeps
+// nothing -, where v is M[c,g] itself (2: the block is read once) or mask_src[c,g] (3).  A row the cell mask removes is not read.
+// The mask never widens the LDS counters' range: a range still holds at most SEL_MAXCELLS cells.
+template <typename T, int NT, bool TWO, int MK = 0>
 __global__ __launch_bounds__(64 * SEL_WAVES) void k_select_count(const T *__restrict__ M, const T *__restrict__ M2,
                                                                   const double *__restrict__ scale_a, const double *__restrict__ scale_b,
                                                                   const uint64_t *__restrict__ prefix, unsigned *__restrict__ hist, int pass,
-                                                                  int C, int per, int G, int64_t ld)
+                                                                  int C, int per, int G, int64_t ld, const T *__restrict__ mask_src = nullptr,
+                                                                  const double *__restrict__ mask_thr = nullptr,
+                                                                  const unsigned char *__restrict__ cell_mask = nullptr, int mask_mode = 0)
 {
+    static_assert(MK == 0 || !TWO, "the masked select takes one matrix");
     using U = typename Key<T>::U;
     constexpr int PASSES = sizeof(U);
     constexpr int UNR = 8;                                         // cells a wave has in flight: their loads are issued before the first is used
@@ -630,19 +664,49 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void k_select_count(const T *__rest
         for (int t = 0; t < NT; ++t) pf[t] = pass == 0 ? (U)0 : (U)(prefix[(int64_t)t * G + g] >> (shift + 8));
         T den_a = T(1), den_b = T(1);
         if (TWO) { den_a = (T)scale_a[g]; den_b = (T)scale_b[g]; }
+        double thr = 0.0;
+        if (MK >= 2) thr = mask_thr[g];
         for (int cb = c0 + wave; cb < c1; cb += SEL_WAVES * UNR) {
             T m[UNR], m2[UNR];
+            unsigned on = (1u << UNR) - 1;                             // MK != 0: bit u = the cell mask keeps cell u's row
+            if constexpr (MK != 0) {
+                // the UNR mask bytes first, so the row loads below wait for them once and not one after the other; a wave's lanes
+                // share the cells, so the bits go to a scalar register and the branches on them are uniform
+                if (cell_mask != nullptr) {
+                    on = 0;
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u) on |= (cell_mask[min(cb + u * SEL_WAVES, c1 - 1)] != 0 ? 1u : 0u) << u;
+                    on = (unsigned)__builtin_amdgcn_readfirstlane((int)on);
+                }
+            }
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 // branch-free: a cell beyond the range re-reads the range's last row (inside the block) and is dropped below
-                const int64_t o = (int64_t)min(cb + u * SEL_WAVES, c1 - 1) * ld + g;
-                m[u] = M[o];
-                m2[u] = TWO ? M2[o] : T(0);
+                const int c = min(cb + u * SEL_WAVES, c1 - 1);
+                const int64_t o = (int64_t)c * ld + g;
+                if constexpr (MK == 0) {
+                    m[u] = M[o];
+                    m2[u] = TWO ? M2[o] : T(0);
+                } else {
+                    m[u] = T(0); m2[u] = T(0);                         // m2: the mask's source when it is not M
+                    if ((on >> u) & 1u) {
+                        m[u] = M[o];
+                        if (MK == 3) m2[u] = mask_src[o];
+                    }
+                }
             }
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 if (cb + u * SEL_WAVES >= c1) break;
-                const U k = Key<T>::enc(zvalue<T>(m[u], m2[u], den_a, den_b, TWO));
+                if constexpr (MK != 0) {
+                    bool keep = (on >> u) & 1u;
+                    if (MK >= 2) {
+                        const double mv = (double)(MK == 2 ? m[u] : m2[u]);
+                        keep = keep && (mask_mode == 1 ? (mv > thr) : (mv <= thr));
+                    }
+                    if (!keep) continue;
+                }
+                const U k = Key<T>::enc(MK == 0 ? zvalue<T>(m[u], m2[u], den_a, den_b, TWO) : m[u]);
                 const unsigned d = (unsigned)((k >> shift) & 0xff);
                 const U hi = pass == 0 ? (U)0 : (U)(k >> ((shift + 8) & (8 * PASSES - 1)));
                 const unsigned inc = 1u << ((d & 1) * 16);
@@ -708,6 +772,85 @@ __global__ void k_select_finish(const uint64_t *__restrict__ prefix, SelArgs sa,
     }
 }
 
+// ---- the masked select: a gene's population n_g is known only after pass 0, whose one histogram counts every kept cell.
+// State: (2 nq, G) uint64 prefixes, (nq, G) fp64 fractions, (G) int64 populations, (2 nq, G) uint32 ranks; targets 2 qi and
+// 2 qi + 1 are the ranks lo and hi of percentile qi.  Until pass 0 ends the fraction's slot holds the percentile itself.
+__global__ void k_mselect_begin(uint64_t *__restrict__ prefix, double *__restrict__ frac, int64_t *__restrict__ pop,
+                                unsigned *__restrict__ rank, QArgs qa, int nq, int G)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    pop[g] = 0;
+    for (int qi = 0; qi < nq; ++qi) {
+        frac[(int64_t)qi * G + g] = qa.q[qi];
+        for (int s = 0; s < 2; ++s) { prefix[(int64_t)(2 * qi + s) * G + g] = 0; rank[(int64_t)(2 * qi + s) * G + g] = 0xffffffffu; }
+    }
+}
+
+// End of pass 0, one wave per (percentile, gene): the histogram's total is n_g; both ranks and the fraction follow with the
+// arithmetic of k_gene_quantiles, and the first digit of both is fixed from the same scan (k_select_advance's).  n_g == 0 leaves
+// the ranks beyond every later histogram, so nothing is ever selected, and k_mselect_finish writes NaN.
+__global__ __launch_bounds__(256) void k_mselect_advance0(uint64_t *__restrict__ prefix, double *__restrict__ frac,
+                                                           int64_t *__restrict__ pop, unsigned *__restrict__ rank,
+                                                           const unsigned *__restrict__ hist, int shift, int nq, int G)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t qg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (qg >= (int64_t)nq * G) return;
+    const int qi = (int)(qg / G), g = (int)(qg % G);
+    const unsigned *h = hist + (int64_t)g * 256 + lane * 4;
+    const unsigned h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3];
+    const unsigned tot = h0 + h1 + h2 + h3;
+    unsigned incl = tot;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    const unsigned excl = incl - tot;
+    const unsigned n = (unsigned)__shfl((int)incl, 63, 64);
+    const double q = frac[qg];
+    if (qi == 0 && lane == 0) pop[g] = (int64_t)n;
+    if (n == 0) {
+        if (lane == 0) frac[qg] = 0.0;
+        return;
+    }
+    const double hh = __dmul_rn((double)(n - 1), q / 100.0);   // numpy: (n-1) * (q/100)
+    const unsigned lo = (unsigned)floor(hh), hi = min(lo + 1, n - 1);
+    if (lane == 0) frac[qg] = hh - (double)lo;
+    const unsigned rks[2] = {lo, hi};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const unsigned rk = rks[s];
+        if (rk >= excl && rk < incl) {   // exactly one lane
+            unsigned r = rk - excl;
+            int d;
+            if (r < h0) d = 0;
+            else if ((r -= h0) < h1) d = 1;
+            else if ((r -= h1) < h2) d = 2;
+            else { r -= h2; d = 3; }
+            const int64_t tg = (int64_t)(2 * qi + s) * G + g;
+            prefix[tg] = (uint64_t)(lane * 4 + d) << shift;
+            rank[tg] = r;
+        }
+    }
+}
+
+template <typename T>
+__global__ void k_mselect_finish(const uint64_t *__restrict__ prefix, const double *__restrict__ frac, const int64_t *__restrict__ pop,
+                                 int nq, double *__restrict__ out, int64_t *__restrict__ counts, int G)
+{
+    using U = typename Key<T>::U;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const int64_t n = pop[g];
+    if (counts) counts[g] = n;
+    for (int qi = 0; qi < nq; ++qi) {
+        const T vlo = Key<T>::dec((U)prefix[(int64_t)(2 * qi) * G + g]), vhi = Key<T>::dec((U)prefix[(int64_t)(2 * qi + 1) * G + g]);
+        out[(int64_t)qi * G + g] = n > 0 ? lerp_numpy((double)vlo, (double)vhi, frac[(int64_t)qi * G + g]) : (double)NAN;
+    }
+}
+
 }  // namespace vcy
 
 using namespace vcy;
@@ -754,7 +897,7 @@ extern "C" int vcy_fit_slope(const void *Y, const void *X, float *gamma, void *w
 
 static int fit_weighted_partials(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
                                  const double *scale_a, const double *scale_b, const double *down, const double *up, void *workspace,
-                                 int64_t C, int64_t G, int64_t ld, int dtype, hipStream_t st)
+                                 int64_t C, int64_t G, int64_t ld, int dtype, hipStream_t st, const unsigned char *cmask = nullptr)
 {
     VCY_REQUIRE(C > 0 && G > 0 && ld >= G, "fit_weighted: bad shape");
     VCY_REQUIRE(dtype == VCY_F32 || dtype == VCY_F64, "fit_weighted: bad dtype");
@@ -764,12 +907,16 @@ static int fit_weighted_partials(const void *Y, const void *X, int weight_mode, 
     VCY_REQUIRE(weight_mode != 1 || ((scale_a == nullptr) == (scale_b == nullptr) && (scale_a == nullptr || M2)), "fit_weighted: scale_a/scale_b/M2 go together");
     dim3 grid((unsigned)((G + 255) / 256), FIT_CB);
 #define VCY_LAUNCH_W(T, MODE)                                                                                                  \
-    hipLaunchKernelGGL((k_moments_weighted<T, MODE>), grid, dim3(256), 0, st, (const T *)Y, (const T *)X, (const T *)W, (const T *)M, \
-                       (const T *)M2, scale_a, scale_b, down, up, (double *)workspace, (int)C, (int)G, ld)
+    if (cmask)                                                                                                                 \
+        hipLaunchKernelGGL((k_moments_weighted_masked<T, MODE>), grid, dim3(256), 0, st, (const T *)Y, (const T *)X, (const T *)W,     \
+                           (const T *)M, (const T *)M2, scale_a, scale_b, down, up, (double *)workspace, (int)C, (int)G, ld, cmask);  \
+    else                                                                                                                       \
+        hipLaunchKernelGGL((k_moments_weighted<T, MODE>), grid, dim3(256), 0, st, (const T *)Y, (const T *)X, (const T *)W, (const T *)M, \
+                           (const T *)M2, scale_a, scale_b, down, up, (double *)workspace, (int)C, (int)G, ld)
     if (dtype == VCY_F32) {
-        if (weight_mode == 0) VCY_LAUNCH_W(float, 0); else if (weight_mode == 1) VCY_LAUNCH_W(float, 1); else VCY_LAUNCH_W(float, 2);
+        if (weight_mode == 0) { VCY_LAUNCH_W(float, 0); } else if (weight_mode == 1) { VCY_LAUNCH_W(float, 1); } else { VCY_LAUNCH_W(float, 2); }
     } else {
-        if (weight_mode == 0) VCY_LAUNCH_W(double, 0); else if (weight_mode == 1) VCY_LAUNCH_W(double, 1); else VCY_LAUNCH_W(double, 2);
+        if (weight_mode == 0) { VCY_LAUNCH_W(double, 0); } else if (weight_mode == 1) { VCY_LAUNCH_W(double, 1); } else { VCY_LAUNCH_W(double, 2); }
     }
 #undef VCY_LAUNCH_W
     VCY_LAUNCH_CHECK();
@@ -799,6 +946,20 @@ extern "C" int vcy_fit_weighted_moments(const void *Y, const void *X, int weight
     VCY_REQUIRE(Y && X && moments && workspace, "fit_weighted_moments: null pointer");
     hipStream_t st = as_stream(stream);
     int rc = fit_weighted_partials(Y, X, weight_mode, W, M, M2, scale_a, scale_b, down, up, workspace, C, G, ld, dtype, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_fit_weighted_fold, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const double *)workspace, moments, (int)G);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_fit_weighted_moments_masked(const void *Y, const void *X, int weight_mode, const void *W, const void *M, const void *M2,
+                                               const double *scale_a, const double *scale_b, const double *down, const double *up,
+                                               const unsigned char *cell_mask, double *moments, void *workspace, int64_t C, int64_t G,
+                                               int64_t ld, int dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && X && moments && workspace && cell_mask, "fit_weighted_moments_masked: null pointer");
+    hipStream_t st = as_stream(stream);
+    int rc = fit_weighted_partials(Y, X, weight_mode, W, M, M2, scale_a, scale_b, down, up, workspace, C, G, ld, dtype, st, cell_mask);
     if (rc) return rc;
     hipLaunchKernelGGL(k_fit_weighted_fold, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const double *)workspace, moments, (int)G);
     VCY_LAUNCH_CHECK();
@@ -927,9 +1088,12 @@ extern "C" int vcy_gene_select_begin(void *state, void *hist, const int64_t *ran
     return VCY_OK;
 }
 
+struct SelMask { const void *src; const double *thr; const unsigned char *cells; int mode, mk; };   // mk: k_select_count's MK
+
 template <typename T>
 static int select_count_launch(const void *M, const void *M2, const double *scale_a, const double *scale_b, const uint64_t *prefix,
-                               unsigned *hist, int pass, int nt, int64_t C, int64_t G, int64_t ld, hipStream_t st)
+                               unsigned *hist, int pass, int nt, int64_t C, int64_t G, int64_t ld, hipStream_t st,
+                               const SelMask &mask = SelMask{nullptr, nullptr, nullptr, 0, 0})
 {
     DevInfo di;
     int rc = device_info(&di);
@@ -949,9 +1113,24 @@ static int select_count_launch(const void *M, const void *M2, const double *scal
         rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);                                                      \
         if (rc) return rc;                                                                                                       \
         hipLaunchKernelGGL(kern, grid, dim3(64 * SEL_WAVES), lds, st, (const T *)M, (const T *)M2, scale_a, scale_b, prefix, hist, pass, \
-                           (int)C, (int)per, (int)G, ld);                                                                        \
+                           (int)C, (int)per, (int)G, ld, (const T *)nullptr, (const double *)nullptr, (const unsigned char *)nullptr, 0); \
     }
-    if (nt == 1) VCY_SEL(1) else if (nt == 2) VCY_SEL(2) else if (nt == 3) VCY_SEL(3) else VCY_SEL(4)
+#define VCY_MSEL(NT, MK)                                                                                                         \
+    {                                                                                                                            \
+        auto kern = k_select_count<T, NT, false, MK>;                                                                            \
+        rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);                                                      \
+        if (rc) return rc;                                                                                                       \
+        hipLaunchKernelGGL(kern, grid, dim3(64 * SEL_WAVES), lds, st, (const T *)M, (const T *)nullptr, (const double *)nullptr,  \
+                           (const double *)nullptr, prefix, hist, pass, (int)C, (int)per, (int)G, ld, (const T *)mask.src, mask.thr, \
+                           mask.cells, mask.mode);                                                                               \
+    }
+#define VCY_MSEL_NT(MK) { if (nt == 1) VCY_MSEL(1, MK) else if (nt == 2) VCY_MSEL(2, MK) else if (nt == 3) VCY_MSEL(3, MK) else VCY_MSEL(4, MK) }
+    if (mask.mk == 1) VCY_MSEL_NT(1)
+    else if (mask.mk == 2) VCY_MSEL_NT(2)
+    else if (mask.mk == 3) VCY_MSEL_NT(3)
+    else if (nt == 1) VCY_SEL(1) else if (nt == 2) VCY_SEL(2) else if (nt == 3) VCY_SEL(3) else VCY_SEL(4)
+#undef VCY_MSEL_NT
+#undef VCY_MSEL
 #undef VCY_SEL
     VCY_LAUNCH_CHECK();
     return VCY_OK;
@@ -1014,6 +1193,105 @@ extern "C" int vcy_gene_select_finish(const void *state, const int *lo_target, c
     hipStream_t st = as_stream(stream);
     if (dtype == VCY_F32) hipLaunchKernelGGL(k_select_finish<float>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const uint64_t *)state, sa, nq, out, (int)G);
     else hipLaunchKernelGGL(k_select_finish<double>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const uint64_t *)state, sa, nq, out, (int)G);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+// ---- masked streamed order statistics (state layout: k_mselect_begin)
+struct MselState { uint64_t *prefix; double *frac; int64_t *pop; unsigned *rank; };
+static MselState msel_state(const void *state, int nq, int64_t G)
+{
+    MselState s;
+    s.prefix = (uint64_t *)state;
+    s.frac = (double *)(s.prefix + (size_t)2 * nq * G);
+    s.pop = (int64_t *)(s.frac + (size_t)nq * G);
+    s.rank = (unsigned *)(s.pop + (size_t)G);
+    return s;
+}
+
+extern "C" size_t vcy_gene_mselect_state_bytes(int64_t G, int nq)
+{
+    return (size_t)G * ((size_t)2 * nq * (sizeof(uint64_t) + sizeof(unsigned)) + (size_t)nq * sizeof(double) + sizeof(int64_t));
+}
+
+static int mselect_args_ok(const void *state, const void *hist, int nq, int64_t G, int dtype)
+{
+    VCY_REQUIRE(nq > 0 && 2 * nq <= SEL_MAXTARGETS, "gene_mselect: nq outside [1,8]");
+    return select_args_ok(state, hist, 2 * nq, G, dtype);
+}
+
+extern "C" int vcy_gene_mselect_begin(void *state, void *hist, const double *qs_host, int nq, int64_t G, int dtype, vcy_stream stream)
+{
+    int rc = mselect_args_ok(state, hist, nq, G, dtype);
+    if (rc) return rc;
+    VCY_REQUIRE(qs_host, "gene_mselect_begin: null pointer");
+    QArgs qa;
+    for (int i = 0; i < 16; ++i) qa.q[i] = i < nq ? qs_host[i] : 0.0;
+    for (int i = 0; i < nq; ++i) VCY_REQUIRE(qs_host[i] >= 0.0 && qs_host[i] <= 100.0, "gene_mselect_begin: percentile outside [0,100]");
+    hipStream_t st = as_stream(stream);
+    const MselState s = msel_state(state, nq, G);
+    hipLaunchKernelGGL(k_mselect_begin, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, s.prefix, s.frac, s.pop, s.rank, qa, nq, (int)G);
+    VCY_LAUNCH_CHECK();
+    VCY_CHECK_HIP(hipMemsetAsync(hist, 0, vcy_gene_select_hist_bytes(G, 2 * nq), st));
+    return VCY_OK;
+}
+
+extern "C" int vcy_gene_mselect_count_block(const void *M, const void *mask_src, const double *mask_thr, int mask_mode,
+                                            const unsigned char *cell_mask, const void *state, void *hist, int pass, int nq, int64_t C,
+                                            int64_t G, int64_t ld, int dtype, vcy_stream stream)
+{
+    int rc = mselect_args_ok(state, hist, nq, G, dtype);
+    if (rc) return rc;
+    VCY_REQUIRE(M, "gene_mselect_count_block: null pointer");
+    VCY_REQUIRE(C > 0 && C <= INT32_MAX && ld >= G, "gene_mselect_count_block: bad shape");
+    VCY_REQUIRE(mask_mode >= 0 && mask_mode <= 2 && (mask_mode == 0 || (mask_src && mask_thr)), "gene_mselect_count_block: bad mask arguments");
+    VCY_REQUIRE(pass >= 0 && pass < vcy_gene_select_passes(dtype), "gene_mselect_count_block: pass outside [0, passes)");
+    hipStream_t st = as_stream(stream);
+    const SelMask mask{mask_src, mask_thr, cell_mask, mask_mode, mask_mode == 0 ? 1 : (mask_src == M ? 2 : 3)};
+    const uint64_t *prefix = (const uint64_t *)state;
+    const int n = pass == 0 ? 1 : 2 * nq;      // pass 0: one histogram, whose total is the gene's population
+    for (int t0 = 0; t0 < n; t0 += SEL_MAXT) {
+        const int nt = std::min(SEL_MAXT, n - t0);
+        unsigned *h = (unsigned *)hist + (size_t)t0 * G * 256;
+        rc = dtype == VCY_F32 ? select_count_launch<float>(M, nullptr, nullptr, nullptr, prefix + (size_t)t0 * G, h, pass, nt, C, G, ld, st, mask)
+                              : select_count_launch<double>(M, nullptr, nullptr, nullptr, prefix + (size_t)t0 * G, h, pass, nt, C, G, ld, st, mask);
+        if (rc) return rc;
+    }
+    return VCY_OK;
+}
+
+extern "C" int vcy_gene_mselect_advance(void *state, void *hist, int pass, int nq, int64_t G, int dtype, vcy_stream stream)
+{
+    int rc = mselect_args_ok(state, hist, nq, G, dtype);
+    if (rc) return rc;
+    const int passes = vcy_gene_select_passes(dtype);
+    VCY_REQUIRE(pass >= 0 && pass < passes, "gene_mselect_advance: pass outside [0, passes)");
+    hipStream_t st = as_stream(stream);
+    const MselState s = msel_state(state, nq, G);
+    const int shift = 8 * (passes - 1 - pass);
+    if (pass == 0) {
+        const int64_t qg = (int64_t)nq * G;
+        hipLaunchKernelGGL(k_mselect_advance0, dim3((unsigned)((qg + 3) / 4)), dim3(256), 0, st, s.prefix, s.frac, s.pop, s.rank,
+                           (const unsigned *)hist, shift, nq, (int)G);
+    } else {
+        const int64_t tg = (int64_t)2 * nq * G;
+        hipLaunchKernelGGL(k_select_advance, dim3((unsigned)((tg + 3) / 4)), dim3(256), 0, st, s.prefix, s.rank, (const unsigned *)hist, shift,
+                           0, 2 * nq, (int)G);
+    }
+    VCY_LAUNCH_CHECK();
+    VCY_CHECK_HIP(hipMemsetAsync(hist, 0, vcy_gene_select_hist_bytes(G, pass == 0 ? 1 : 2 * nq), st));
+    return VCY_OK;
+}
+
+extern "C" int vcy_gene_mselect_finish(const void *state, int nq, double *out, int64_t *counts, int64_t G, int dtype, vcy_stream stream)
+{
+    int rc = mselect_args_ok(state, state, nq, G, dtype);
+    if (rc) return rc;
+    VCY_REQUIRE(out, "gene_mselect_finish: null pointer");
+    hipStream_t st = as_stream(stream);
+    const MselState s = msel_state(state, nq, G);
+    if (dtype == VCY_F32) hipLaunchKernelGGL(k_mselect_finish<float>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, s.prefix, s.frac, s.pop, nq, out, counts, (int)G);
+    else hipLaunchKernelGGL(k_mselect_finish<double>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, s.prefix, s.frac, s.pop, nq, out, counts, (int)G);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
 }

@@ -2152,6 +2152,123 @@ class StreamedGeneQuantiles:
         return out
 
 
+def _cell_mask_u8(cell_mask, C: int, dev, who: str) -> Optional[torch.Tensor]:
+    """A per-cell mask as the uint8 (C) device vector the kernels read (non-zero = the cell counts); None stays None."""
+    if cell_mask is None:
+        return None
+    m = torch.as_tensor(cell_mask, device=dev)
+    if m.ndim != 1 or m.numel() != C:
+        raise ValueError(f"{who}: cell_mask must hold one value per cell of the block ({C}), got shape {tuple(m.shape)}")
+    return (m != 0).to(torch.uint8).contiguous()
+
+
+class StreamedMaskedGeneQuantiles:
+    """StreamedGeneQuantiles under a mask (vcy_gene_mselect_*): per gene, np.percentile(M[keep, g], qs) over the cells a value mask
+    and / or a cell mask keep - ops.gene_quantiles(M, qs, mask_src=, mask_thr=, mask_mode=) on the (gathered) whole matrix, bit for
+    bit on finite data - from cell blocks, with O(genes) memory.  A gene's population is the number of its kept cells; it is known
+    after the first pass, whose histogram totals give it, and the ranks are derived on the device then: no extra walk over the data.
+    One pass = add_block() on EVERY block with the SAME masks (any order, any blocking; the cells of all ranks in a cell-sharded
+    run), then advance(); when `done`, result() is the (len(qs), G) float64 tensor (NaN where no cell is kept) and counts() the
+    (G,) int64 populations.  At most 8 percentiles."""
+
+    def __init__(self, G: int, qs: Sequence[float], dtype=None, device=None):
+        self.G = int(G)
+        self.qs = [float(q) for q in np.asarray(qs, dtype=np.float64).ravel()]
+        if not self.qs or len(self.qs) > 8:
+            raise ValueError("StreamedMaskedGeneQuantiles: between 1 and 8 percentiles")
+        for q in self.qs:
+            if not 0.0 <= q <= 100.0:          # also refuses NaN
+                raise ValueError(f"StreamedMaskedGeneQuantiles: percentile {q} outside [0, 100]")
+        self.nq, self.nt = len(self.qs), 2 * len(self.qs)
+        self.dtype = resolve_dtype(dtype)
+        self.code = _DT[self.dtype]
+        self.dev = require_gpu() if device is None else torch.device(device)
+        L = _lib.lib()
+        self.passes = int(L.vcy_gene_select_passes(self.code))
+        self.state = torch.empty(int(L.vcy_gene_mselect_state_bytes(self.G, self.nq)) // 4, dtype=torch.int32, device=self.dev)
+        self.hist = torch.empty((self.nt, self.G, 256), dtype=torch.int32, device=self.dev)       # int32: what the ranks' counts are summed in
+        _lib.check(L.vcy_gene_mselect_begin(self.state.data_ptr(), self.hist.data_ptr(), (ctypes.c_double * self.nq)(*self.qs), self.nq,
+                                            self.G, self.code, _stream()), "gene_mselect_begin")
+        self.pass_no = 0
+        self._cells = 0          # cells (rows, masked or not) this rank added in the current pass
+        self.n_cells = None      # ... and over all ranks in every finished pass
+
+    @property
+    def done(self) -> bool:
+        return self.pass_no >= self.passes
+
+    @property
+    def state_bytes(self) -> int:
+        return self.state.numel() * 4 + self.hist.numel() * 4
+
+    def add_block(self, M: CellMatrix, mask_src: Optional[CellMatrix] = None, mask_thr: Optional[torch.Tensor] = None, mask_mode: int = 0,
+                  cell_mask=None) -> None:
+        who = "StreamedMaskedGeneQuantiles.add_block"
+        if self.done:
+            raise RuntimeError(f"{who}: every pass is done")
+        if M.G != self.G or (mask_src is not None and (mask_src.G != self.G or mask_src.C != M.C or mask_src.ld != M.ld)):
+            raise ValueError(f"{who}: a block of {M.G} genes for a select over {self.G} genes (or mask_src of another shape)")
+        if M.dtype != self.dtype or (mask_src is not None and mask_src.dtype != self.dtype):
+            raise ValueError(f"{who}: block dtype {M.dtype}, select dtype {self.dtype}")
+        if mask_mode not in (0, 1, 2):
+            raise ValueError(f"{who}: mask_mode {mask_mode!r} (0 none, 1 keeps mask_src > mask_thr, 2 keeps mask_src <= mask_thr)")
+        if (mask_mode != 0) != (mask_src is not None) or (mask_mode != 0) != (mask_thr is not None):
+            raise ValueError(f"{who}: mask_src and mask_thr go with mask_mode 1 or 2, and only with them")
+        cm = _cell_mask_u8(cell_mask, M.C, self.dev, who)
+        if M.C == 0:
+            return
+        if mask_thr is not None:
+            mask_thr = mask_thr.to(device=self.dev, dtype=torch.float64).contiguous()
+            if mask_thr.numel() != self.G:
+                raise ValueError(f"{who}: mask_thr must hold one value per gene")
+        src_ptr = None if mask_src is None else mask_src.t.data_ptr()          # the same storage as M: the kernel reads the block once
+        _lib.check(_lib.lib().vcy_gene_mselect_count_block(M.t.data_ptr(), src_ptr, _p(mask_thr), int(mask_mode), _p(cm), self.state.data_ptr(),
+                                                           self.hist.data_ptr(), self.pass_no, self.nq, M.C, self.G, M.ld, self.code,
+                                                           _stream()), "gene_mselect_count_block")
+        self._cells += M.C
+
+    def advance(self, group=None) -> None:
+        """Ends a pass: sums the integer histograms (and the cell counts) over the ranks, then fixes the next digit of every target;
+        the first pass also turns the histogram totals into the genes' populations, ranks and fractions."""
+        from . import distributed as D
+        who = "StreamedMaskedGeneQuantiles.advance"
+        if self.done:
+            raise RuntimeError(f"{who}: every pass is done")
+        cells = self._cells
+        if D.active():
+            cells = int(D.all_reduce_sum(torch.tensor([cells], dtype=torch.int64, device=self.dev), group).item())
+        if cells == 0:
+            raise RuntimeError(f"{who}: no block was added in this pass")
+        if cells > 2 ** 31 - 1:
+            raise ValueError(f"{who}: {cells} cells in one pass, the counters are 32-bit (at most 2^31 - 1)")
+        if self.n_cells is not None and cells != self.n_cells:
+            raise ValueError(f"{who}: the pass saw {cells} cells, the first pass saw {self.n_cells}")
+        self.n_cells = cells
+        D.all_reduce_sum(self.hist[:1] if self.pass_no == 0 else self.hist, group)      # pass 0 counts one histogram for all targets
+        _lib.check(_lib.lib().vcy_gene_mselect_advance(self.state.data_ptr(), self.hist.data_ptr(), self.pass_no, self.nq, self.G, self.code,
+                                                       _stream()), "gene_mselect_advance")
+        self.pass_no += 1
+        self._cells = 0
+
+    def _finish(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        out = torch.empty((self.nq, self.G), dtype=torch.float64, device=self.dev)
+        n = torch.empty(self.G, dtype=torch.int64, device=self.dev)
+        _lib.check(_lib.lib().vcy_gene_mselect_finish(self.state.data_ptr(), self.nq, out.data_ptr(), n.data_ptr(), self.G, self.code,
+                                                      _stream()), "gene_mselect_finish")
+        return out, n
+
+    def result(self) -> torch.Tensor:
+        if not self.done:
+            raise RuntimeError(f"StreamedMaskedGeneQuantiles.result: {self.pass_no} of {self.passes} passes done")
+        return self._finish()[0]
+
+    def counts(self) -> torch.Tensor:
+        """(G,) int64: the number of cells kept per gene (known from the end of the first pass on)."""
+        if self.pass_no < 1:
+            raise RuntimeError("StreamedMaskedGeneQuantiles.counts: the first pass is not done")
+        return self._finish()[1]
+
+
 def fit_weighted(Y: CellMatrix, X: CellMatrix, weight_mode: int, W: Optional[CellMatrix] = None, M: Optional[CellMatrix] = None,
                  M2: Optional[CellMatrix] = None, scale_a=None, scale_b=None, down=None, up=None, fit_offset: bool = True,
                  box_q: bool = True, lo_gamma: float = 1e-8, up_gamma_default: float = 20.0, up_gamma=None, q_fixed=None,
@@ -2173,14 +2290,23 @@ def fit_weighted(Y: CellMatrix, X: CellMatrix, weight_mode: int, W: Optional[Cel
 
 
 def fit_weighted_moments(Y: CellMatrix, X: CellMatrix, weight_mode: int, W: Optional[CellMatrix] = None, M: Optional[CellMatrix] = None,
-                         M2: Optional[CellMatrix] = None, scale_a=None, scale_b=None, down=None, up=None) -> torch.Tensor:
+                         M2: Optional[CellMatrix] = None, scale_a=None, scale_b=None, down=None, up=None, cell_mask=None) -> torch.Tensor:
     """First half of fit_weighted for a block of cells (vcy_fit_weighted_moments): (10, G) fp64 moments [Sx Sy Sxx Sxy Syy | Sw Swx
-    Swy Swxx Swxy] that add up over blocks (an all-reduce in cell-sharded runs) before fit_weighted_from_moments solves them."""
+    Swy Swxx Swxy] that add up over blocks (an all-reduce in cell-sharded runs) before fit_weighted_from_moments solves them.
+    cell_mask (one value per cell of the block): only the cells with a non-zero entry are summed (vcy_fit_weighted_moments_masked;
+    the rows of the others are not read); an all-ones mask gives the unmasked moments bit for bit."""
     dev = Y.t.device
     mom = torch.empty((10, Y.G), dtype=torch.float64, device=dev)
     ws = _fit_workspace(Y.G, dev)
     f64 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float64).contiguous()
     scale_a, scale_b, down, up = map(f64, (scale_a, scale_b, down, up))
+    if cell_mask is not None:
+        cm = _cell_mask_u8(cell_mask, Y.C, dev, "fit_weighted_moments")
+        _lib.check(_lib.lib().vcy_fit_weighted_moments_masked(Y.t.data_ptr(), X.t.data_ptr(), weight_mode, None if W is None else W.t.data_ptr(),
+                                                              None if M is None else M.t.data_ptr(), None if M2 is None else M2.t.data_ptr(),
+                                                              _p(scale_a), _p(scale_b), _p(down), _p(up), cm.data_ptr(), mom.data_ptr(),
+                                                              ws.data_ptr(), Y.C, Y.G, Y.ld, Y.code, _stream()), "fit_weighted_moments_masked")
+        return mom
     _lib.check(_lib.lib().vcy_fit_weighted_moments(Y.t.data_ptr(), X.t.data_ptr(), weight_mode, None if W is None else W.t.data_ptr(),
                                                    None if M is None else M.t.data_ptr(), None if M2 is None else M2.t.data_ptr(),
                                                    _p(scale_a), _p(scale_b), _p(down), _p(up), mom.data_ptr(), ws.data_ptr(), Y.C, Y.G, Y.ld,
