@@ -78,7 +78,8 @@ const char *vcy_last_error(void);
  * value a version-4 caller passes is still accepted, so the version stays; such a caller's VCY_RULES_PARTIAL on VCY_SQRT / VCY_F64 now gets
  * the one-correction root described at vcy_rules.)  (Gene selection from CSR layers added vcy_csr_gene_stats_block_cells,
  * vcy_csr_gene_stats_workspace_bytes, vcy_csr_gene_stats, vcy_csr_select_count and vcy_csr_select_fill: additions only, the version stays.
- * So are the vcy_loom_tile_* entries and vcy_loom_block_host.) */
+ * So are the vcy_loom_tile_* entries and vcy_loom_block_host, and the winsorised gene selection from CSR layers: vcy_csr_gene_stats_parts*,
+ * vcy_csr_gene_stats_clip and vcy_csr_quantiles_*.) */
 int vcy_abi_version(void);
 /* Number of CUs / LDS bytes per workgroup of the current device (host query). */
 int vcy_device_info(int *cu_count, int *lds_bytes_per_block, int64_t *hbm_bytes);
@@ -808,6 +809,50 @@ int vcy_csr_select_count(const int64_t *indptr, const int32_t *indices, const in
                          vcy_stream stream);
 int vcy_csr_select_fill(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *remap, const int64_t *indptr_out,
                         int32_t *indices_out, void *data_out, int64_t C, int64_t G, int count_dtype, vcy_stream stream);
+
+/* ---------------------------------------------------------------- upstream caller: winsorised gene selection from CSR count layers
+ * score_cv_vs_mean(winsorize=True) (analysis.py:255-298: np.percentile of every gene over the cells, np.clip to the two percentiles,
+ * mean and std of the clipped values) where the layer only exists as cells-major CSR counts.  Arrays as for vcy_csr_gene_stats.
+ *
+ * vcy_csr_gene_stats_parts (analysis.py:255-298): parts (6, G) int64 = per gene, over the cells with cell_mask != 0, [n_below = positive
+ * counts < lo[g], n_above = counts > hi[g], sum and sum of squares of the other positive counts, number of positive counts, largest
+ * count] - integers accumulated in LDS per tile and added per gene (workspace: vcy_csr_gene_stats_parts_workspace_bytes(C, G) bytes,
+ * 8-byte aligned), so they do not depend on order, blocking or sharding: a cell-sharded caller adds rows 0-4 and maximises row 5 over
+ * its ranks.  lo, hi: G f64 each, both or neither (NULL: nothing is clipped); lo <= hi is the caller's to keep.
+ * vcy_csr_gene_stats_clip (analysis.py:255-298): stats (4, G) f64 = the rows of vcy_gene_stats(lo, hi) - sum, sum of squares, count(> 0)
+ * and maximum of the CLIPPED values over n_cells cells, the z = n_cells - positive counts zeros included - from parts, with every product
+ * and sum rounded on its own, in this order:  sum = (lo (n_below + [lo > 0] z) + S1) + hi n_above;  sum of squares =
+ * ((lo lo) (n_below + [lo > 0] z) + S2) + (hi hi) n_above;  count = [hi > 0] (positive counts + [lo > 0] z);  max = min(max(largest, lo), hi).
+ * With lo == hi == NULL (or n_cells == 0) the rows are S1, S2, positive counts, largest: vcy_csr_gene_stats' own.
+ *
+ * vcy_csr_quantiles_* (analysis.py:255-298, the np.percentile call at :264): exact order statistics per gene over n_cells selected cells,
+ * zeros included - rank r is 0 when r < z, the (r - z)-th smallest positive stored count otherwise - by an MSB-first radix select on
+ * 8-bit digits: vcy_csr_quantiles_passes(count_dtype) counting walks (1 for VCY_U8, 2 for VCY_U16), each one read of the layer in
+ * tiles of vcy_csr_quantiles_block_cells() cells x slabs of vcy_csr_slab_genes() genes, integer adds only.  hist:
+ * vcy_csr_quantiles_hist_bytes(G, ntargets, count_dtype) bytes = G x 256 uint32 x (1 + ntargets for VCY_U16), as (1 + ntargets, G, 256);
+ * state: vcy_csr_quantiles_state_bytes(G, ntargets) bytes (two uint32 per target and gene).  ntargets <= 32 distinct ranks, ascending,
+ * the same for every gene (ranks_host; numpy's 'linear' rule gives two per percentile).  Order: begin (zeroes hist); for every pass:
+ * count on every block of cells (any order, any blocking; a cell-sharded caller then adds hist[0], after pass 0, or hist[1:], after
+ * pass 1, over its ranks), then advance with n_cells = the selected cells of ALL blocks; then finish: out (nq, G) f64 = numpy's lerp
+ * (the helper of vcy_gene_quantiles) between targets lo_target[i] and hi_target[i] at fraction t_host[i], nq <= 16.  Nothing is
+ * read back to the host in between. */
+size_t vcy_csr_gene_stats_parts_workspace_bytes(int64_t C, int64_t G);
+int vcy_csr_gene_stats_parts(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *slabptr, const uint8_t *cell_mask,
+                             const double *lo, const double *hi, int64_t *parts, void *workspace, int64_t C, int64_t G, int count_dtype,
+                             vcy_stream stream);
+int vcy_csr_gene_stats_clip(const int64_t *parts, const double *lo, const double *hi, int64_t n_cells, double *stats, int64_t G,
+                            vcy_stream stream);
+int64_t vcy_csr_quantiles_block_cells(void);
+int vcy_csr_quantiles_passes(int count_dtype);
+size_t vcy_csr_quantiles_state_bytes(int64_t G, int ntargets);
+size_t vcy_csr_quantiles_hist_bytes(int64_t G, int ntargets, int count_dtype);
+int vcy_csr_quantiles_begin(void *hist, int ntargets, int64_t G, int count_dtype, vcy_stream stream);
+int vcy_csr_quantiles_count(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *slabptr, const uint8_t *cell_mask,
+                            void *hist, int pass, int ntargets, int64_t C, int64_t G, int count_dtype, vcy_stream stream);
+int vcy_csr_quantiles_advance(void *state, void *hist, const int64_t *ranks_host, int pass, int ntargets, int64_t n_cells, int64_t G,
+                              int count_dtype, vcy_stream stream);
+int vcy_csr_quantiles_finish(const void *state, const int *lo_target, const int *hi_target, const double *t_host, int nq, int ntargets,
+                             double *out, int64_t G, vcy_stream stream);
 
 /* ---------------------------------------------------------------- upstream caller: .loom ingest in blocks of cells
  * VelocytoLoom.__init__ (analysis.py:56-67) reads /layers/spliced, unspliced, ambiguous whole, as float64, and sums them per cell.  Here

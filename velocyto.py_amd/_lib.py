@@ -116,6 +116,17 @@ SIGNATURES = {
     "vcy_csr_gene_stats": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
     "vcy_csr_select_count": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "vcy_csr_select_fill": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
+    "vcy_csr_gene_stats_parts_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vcy_csr_gene_stats_parts": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
+    "vcy_csr_gene_stats_clip": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "vcy_csr_quantiles_block_cells": (c_i64, []),
+    "vcy_csr_quantiles_passes": (c_int, [c_int]),
+    "vcy_csr_quantiles_state_bytes": (c_sz, [c_i64, c_int]),
+    "vcy_csr_quantiles_hist_bytes": (c_sz, [c_i64, c_int, c_int]),
+    "vcy_csr_quantiles_begin": (c_int, [c_vp, c_int, c_i64, c_int, c_vp]),
+    "vcy_csr_quantiles_count": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_int, c_vp]),
+    "vcy_csr_quantiles_advance": (c_int, [c_vp, c_vp, ctypes.POINTER(c_i64), c_int, c_int, c_i64, c_i64, c_int, c_vp]),
+    "vcy_csr_quantiles_finish": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), c_int, c_int, c_vp, c_i64, c_vp]),
     "vcy_loom_tile_slab_genes": (c_i64, []),
     "vcy_loom_tile_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vcy_loom_tile_count": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),

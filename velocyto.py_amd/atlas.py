@@ -730,19 +730,88 @@ def score_detection_levels(cS: ops.CsrCounts, cU: ops.CsrCounts, min_expr_counts
     return detection_mask(gene_stats(cS), gene_stats(cU), min_expr_counts, min_cells_express, min_expr_counts_U, min_cells_express_U)
 
 
+def _selected_cells(c: ops.CsrCounts, cell_mask) -> int:
+    """Cells of the whole dataset that cell_mask keeps (all of them when it is None): the ranks' numbers added."""
+    mask = ops._csr_cell_mask(c, cell_mask)
+    n = torch.tensor([c.C if mask is None else int((mask != 0).sum())], dtype=torch.int64, device=c.indptr.device)
+    D.all_reduce_sum(n)
+    return int(n[0])
+
+
+def _same_width(c: ops.CsrCounts) -> ops.CsrCounts:
+    """The layer with uint16 counts when ANY rank's shard holds them (a shard narrows on its own; the select's passes must agree)."""
+    wide = torch.tensor([1.0 if c.code == ops.U16 else 0.0], dtype=torch.float64, device=c.indptr.device)
+    D.all_reduce_max(wide)
+    if float(wide[0]) == 0.0 or c.code == ops.U16:
+        return c
+    w = ops.CsrCounts(c.indptr, c.indices, c.data.to(torch.int16), c.G)
+    w._slabptr = c._slabptr
+    return w
+
+
+def _gene_percentiles(c: ops.CsrCounts, qs, cell_mask, n_total: int) -> torch.Tensor:
+    if n_total == 0:
+        raise ValueError("gene_percentiles: no cell is selected")
+    c = _same_width(c)
+    sel = ops.CsrGeneQuantiles(c.G, qs, n_total, c.code == ops.U16, c.indptr.device)
+    while not sel.done:
+        sel.add_block(c, cell_mask)
+        sel.advance()
+    return sel.result()
+
+
+def gene_percentiles(c: ops.CsrCounts, qs, cell_mask=None) -> np.ndarray:
+    """np.percentile(dense layer, qs, axis=cells) -> (len(qs), G) float64 over ALL ranks' cells (of the masked ones), zeros included, on
+    the host: ops.CsrGeneQuantiles with the integer histograms all-reduced between the digit passes, so the bits are the one-rank
+    bits for any sharding."""
+    return _gene_percentiles(c, qs, cell_mask, _selected_cells(c, cell_mask)).cpu().numpy()
+
+
+def check_winsor_perc(winsor_perc) -> Tuple[float, float]:
+    try:
+        w = [float(v) for v in winsor_perc]
+    except (TypeError, ValueError):
+        w = []
+    if len(w) != 2 or not (0.0 <= w[0] <= w[1] <= 100.0):
+        raise ValueError(f"winsor_perc must be two ascending percentiles in [0, 100], got {winsor_perc!r}")
+    return w[0], w[1]
+
+
+def winsorized_gene_stats(c: ops.CsrCounts, winsor_perc=(1, 99.5), cell_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+    """analysis.py:262-267 on a CSR layer: (moments, bounds) on the host - bounds (2, G) = the two per-gene percentiles, moments (4, G) =
+    [sum, sum of squares, count(> 0), max] of the counts clipped to them, over ALL ranks' cells (of the masked ones).  The integer parts
+    (ops.csr_gene_stats_parts) are all-reduced and folded afterwards (ops.csr_gene_stats_clip): the one-rank bits for any sharding."""
+    winsor_perc = check_winsor_perc(winsor_perc)
+    n_total = _selected_cells(c, cell_mask)
+    q = _gene_percentiles(c, winsor_perc, cell_mask, n_total)
+    parts = ops.csr_gene_stats_parts(c, cell_mask, q[0], q[1])
+    if D.active():
+        D.all_reduce_sum(parts[:5])
+        D.all_reduce_max(parts[5])
+    return ops.csr_gene_stats_clip(parts, n_total, q[0], q[1]).cpu().numpy(), q.cpu().numpy()
+
+
 def score_cv_vs_mean(c: ops.CsrCounts, C_total: Optional[int] = None, N: int = 3000, min_expr_cells: int = 2, max_expr_avg: float = 20,
                      min_expr_avg: float = 0, svr_gamma: Optional[float] = None, sort_inverse: bool = False,
-                     winsorize: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     winsorize: bool = False, winsor_perc=None) -> Tuple[np.ndarray, np.ndarray]:
     """analysis.py:201-345 on a CSR layer: (score, mask) = the facade's (cv_mean_score, cv_mean_selected); the SVR noise model
-    (preprocess.DeviceSVR) is fitted on every rank on the same points.  C_total: cells of the whole dataset (all-reduced when None)."""
-    if winsorize:
-        raise NotImplementedError("score_cv_vs_mean(winsorize=True) on CSR layers: the per-gene percentiles of a gene's stored counts over "
-                                  "the cells of a cells-major CSR are a separate piece of work (a streamed select over the layer); densify "
-                                  "and use VelocytoLoom.score_cv_vs_mean, or leave winsorize off")
+    (preprocess.DeviceSVR) is fitted on every rank on the same points.  C_total: cells of the whole dataset (all-reduced when None).
+    winsor_perc = (lower, upper) switches the winsorisation on, whatever `winsorize` says (the mean and the spread are those of the
+    counts clipped to the gene's two percentiles, winsorized_gene_stats); winsorize=True without it still raises NotImplementedError."""
+    if winsor_perc is None and winsorize:
+        raise NotImplementedError("score_cv_vs_mean(winsorize=True) on CSR layers: name the per-gene percentiles, winsor_perc=(lower, upper) "
+                                  "(the reference's default is (1, 99.5)); winsorize alone stays refused on this route")
     from .preprocess import cv_vs_mean_from_stats
+    moments = None
+    if winsor_perc is not None:
+        winsor_perc = check_winsor_perc(winsor_perc)
     C_total = total_cells(c) if C_total is None else int(C_total)
+    if winsor_perc is not None:
+        if min_expr_cells <= ((100 - winsor_perc[1]) * C_total * 0.01):
+            min_expr_cells = int(np.ceil((100 - winsor_perc[1]) * c.G * 0.01)) + 2          # sic: genes, as the reference (analysis.py:248)
+        moments = winsorized_gene_stats(c, winsor_perc)[0]
     return cv_vs_mean_from_stats(gene_stats(c), C_total, N=N, min_expr_cells=min_expr_cells, max_expr_avg=max_expr_avg,
-                                 min_expr_avg=min_expr_avg, svr_gamma=svr_gamma, sort_inverse=sort_inverse)
+                                 min_expr_avg=min_expr_avg, svr_gamma=svr_gamma, sort_inverse=sort_inverse, moments=moments)
 
 
 def score_cluster_expression(cS: ops.CsrCounts, cU: ops.CsrCounts, cluster_ix, n_clusters: int, min_avg_U: float = 0.02,
@@ -785,11 +854,14 @@ def default_gene_thresholds(C_total: int, **given) -> Dict[str, float]:
     return {**{k: t[k] for k in GENE_FILTER_THRESHOLDS}, **{k: v for k, v in given.items() if v is not None}}
 
 
-def default_gene_filter(cS: ops.CsrCounts, cU: ops.CsrCounts, cluster_ix=None, n_clusters: int = 0, **thresholds):
+def default_gene_filter(cS: ops.CsrCounts, cU: ops.CsrCounts, cluster_ix=None, n_clusters: int = 0, winsor_perc=None, **thresholds):
     """The gene filters of default_filter_and_norm (analysis.py:1889-1940) on CSR layers, in its order: detection filter -> CV-vs-mean at
     max_expr_avg = 40 -> detection filter on the unspliced layer with the halved thresholds, joined with the per-cluster expression
     filter when clusters are given.  Returns (cS', cU', kept): the selected layers and the int64 gene numbers they hold, into the
-    layers as given (to subset the row attributes).  It stops before the normalisations: size_factors(cS'.row_sums(), ...) follows."""
+    layers as given (to subset the row attributes).  It stops before the normalisations: size_factors(cS'.row_sums(), ...) follows.
+    winsor_perc: handed to the CV-vs-mean step (score_cv_vs_mean)."""
+    if winsor_perc is not None:
+        winsor_perc = check_winsor_perc(winsor_perc)
     C_total = total_cells(cS)
     t = default_gene_thresholds(C_total, **thresholds)
     kept = np.arange(cS.G, dtype=np.int64)
@@ -799,7 +871,7 @@ def default_gene_filter(cS: ops.CsrCounts, cU: ops.CsrCounts, cluster_ix=None, n
         cS, cU = select_genes(mask, cS, cU)
         kept = kept[mask]
     cut(score_detection_levels(cS, cU, min_expr_counts=t["min_expr_counts"], min_cells_express=t["min_cells_express"]))
-    cut(score_cv_vs_mean(cS, C_total, N=t["N"], max_expr_avg=40)[1])
+    cut(score_cv_vs_mean(cS, C_total, N=t["N"], max_expr_avg=40, winsor_perc=winsor_perc)[1])
     half = lambda x: int(x / 2) + 1
     mask = score_detection_levels(cS, cU, min_expr_counts=0, min_cells_express=0, min_expr_counts_U=half(t["min_expr_counts"]),
                                   min_cells_express_U=half(t["min_cells_express"]))

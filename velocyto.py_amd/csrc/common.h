@@ -169,6 +169,20 @@ template <typename T> __device__ __forceinline__ T block_sum(T v, T *scratch)
     return r;
 }
 
+// numpy's _lerp between two order statistics a = v[lo], b = v[lo + 1] at fraction t, without fma contraction so that the rounding
+// matches numpy's mul-then-add; t == 0 returns a itself (also when b is infinite).  Shared by every percentile kernel (fit.hip,
+// csr_quantiles.hip).  Plain operators under the pragma: hipcc honours it for the operations written here, but not for those inside
+// the __dmul_rn / __dadd_rn wrappers, whose multiply and add it fuses once they are inlined side by side.
+__device__ __forceinline__ double lerp_numpy(double a, double b, double t)
+{
+#pragma clang fp contract(off)
+    const double diff = b - a;
+    double r = a + diff * t;
+    if (t >= 0.5) r = b - diff * (1.0 - t);
+    if (t == 0.0) r = a;
+    return r;
+}
+
 inline hipStream_t as_stream(vcy_stream s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- process-wide facts, each computed once under a lock and then only read (layout.hip): nothing a call can observe

@@ -24,6 +24,9 @@
 // An explicitly stored zero counts in nothing (sums + 0, no detection, max unchanged): it is skipped.  Genes with nothing stored (and
 // every gene when no cell is selected) come out 0, 0, 0, 0.
 //
+// k_csr_gene_stats_parts / k_csr_gene_stats_clip: the same statistics of the counts clipped to per-gene bounds (the winsorised values of
+// score_cv_vs_mean, analysis.py:255-298), described where they stand below.  The element walk all of them share is csr_walk.h's.
+//
 // k_csr_select_count / k_csr_select_fill: the CSR of the columns with remap[g] >= 0, renumbered remap[g].  A wave per row; 64 stored
 // elements at a time, kept elements compacted in order by ballot + prefix count, so the row's element order is preserved (ascending
 // output indices for a monotone remap).  Rows are NOT cut into chunks: a row of a cells-major layer holds at most G elements (a few
@@ -33,6 +36,7 @@
 // Every position is clamped to [0, indptr[C]) on the way in and to the row's output range on the way out: malformed tables yield wrong
 // numbers, never an access outside the arrays.
 #include "common.h"
+#include "csr_walk.h"
 
 namespace vcy {
 
@@ -52,7 +56,6 @@ __global__ __launch_bounds__(64 * GS_WAVES) void k_csr_gene_stats(const int64_t 
 {
     __shared__ unsigned long long a_sum[GS_SLAB], a_sq[GS_SLAB];
     __shared__ unsigned a_cnt[GS_SLAB], a_max[GS_SLAB];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t tile = blockIdx.x;
     const int slab = blockIdx.y, g0 = slab * GS_SLAB;
     for (int g = threadIdx.x; g < GS_SLAB; g += 64 * GS_WAVES) { a_sum[g] = 0; a_sq[g] = 0; a_cnt[g] = 0; a_max[g] = 0; }
@@ -65,52 +68,7 @@ __global__ __launch_bounds__(64 * GS_WAVES) void k_csr_gene_stats(const int64_t 
         atomicAdd(&a_cnt[g], 1u);
         atomicMax(&a_max[g], x);
     };
-    // A wave takes 64 rows at a time, lane = row: the rows' facts (mask byte, start and length of the slab's segment) are ONE round
-    // trip for 64 rows, and masked-out or empty rows cost nothing after it.  The rows with something in the slab are then walked
-    // GS_ROWS at a time: the first GS_NZ x 64 elements of each are requested together - the request phase is nothing but loads, so
-    // GS_ROWS x GS_NZ x 2 of them are in flight per lane before the first atomic waits - and applied; longer segments finish in a loop.
-    for (int64_t r0 = c0 + (int64_t)wave * 64; r0 < c1; r0 += 64 * GS_WAVES) {
-        const int64_t r = r0 + lane;
-        int64_t a_l = 0;
-        int n_l = 0;
-        if (r < c1 && (!cell_mask || cell_mask[r])) {
-            const int32_t *sp = slabptr + r * (nslab + 1) + slab;
-            a_l = indptr[r] + sp[0];
-            n_l = sp[1] - sp[0];
-            if (a_l < 0 || a_l >= nnz || n_l < 0) n_l = 0;    // every position stays inside [0, nnz)
-            n_l = (int)min((int64_t)n_l, nnz - a_l);
-        }
-        unsigned long long todo = __ballot(n_l > 0);
-        while (todo) {
-            int64_t a[GS_ROWS];
-            int n[GS_ROWS];
-            int gi[GS_ROWS][GS_NZ];
-            unsigned xv[GS_ROWS][GS_NZ];
-#pragma unroll
-            for (int q = 0; q < GS_ROWS; ++q) {
-                const int u = todo ? __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1) : 0;
-                n[q] = todo ? __builtin_amdgcn_readlane(n_l, u) : 0;
-                a[q] = ((int64_t)__builtin_amdgcn_readlane((int)(a_l >> 32), u) << 32) | (unsigned)__builtin_amdgcn_readlane((int)a_l, u);
-                todo &= todo - 1;
-#pragma unroll
-                for (int k = 0; k < GS_NZ; ++k) {
-                    const int t = k * 64 + lane;
-                    gi[q][k] = -1;
-                    xv[q][k] = 0u;
-                    if (t < n[q]) {
-                        gi[q][k] = indices[a[q] + t] - g0;
-                        xv[q][k] = (unsigned)data[a[q] + t];
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < GS_ROWS; ++q) {
-#pragma unroll
-                for (int k = 0; k < GS_NZ; ++k) add((unsigned)gi[q][k], xv[q][k]);
-                for (int t = GS_NZ * 64 + lane; t < n[q]; t += 64) add((unsigned)(indices[a[q] + t] - g0), (unsigned)data[a[q] + t]);
-            }
-        }
-    }
+    csr_slab_walk<CT, GS_WAVES, GS_ROWS, GS_NZ>(indptr, indices, data, slabptr, cell_mask, c0, c1, nnz, slab, nslab, g0, add);
     __syncthreads();
     const int64_t o = tile * G;
     for (int g = threadIdx.x; g < GS_SLAB && g0 + g < G; g += 64 * GS_WAVES) {
@@ -152,6 +110,124 @@ __global__ __launch_bounds__(64 * GS_FOLD) void k_csr_gene_stats_fold(const unsi
     stats[(int64_t)G + g] = (double)ss;
     stats[2 * (int64_t)G + g] = (double)n;
     stats[3 * (int64_t)G + g] = (double)mx;
+}
+
+// ---- the statistics of the counts clipped to per-gene bounds [lo, hi] (score_cv_vs_mean's winsorised values, analysis.py:255-298).
+// k_csr_gene_stats_parts keeps, per gene, integers only: n_below = positive counts < lo, n_above = counts > hi, the sum and the sum of
+// squares of the others, the number of positive counts and their maximum.  A count is an integer, so x < lo is x <= ceil(lo) - 1 and
+// x > hi is x > floor(hi): the two bounds go to LDS as 16-bit integers in one word per gene (clamped to 0..65535, which loses nothing:
+// ceil(lo) - 1 >= 65535 puts every count below, floor(hi) < 0 every positive count above).  A count above hi is counted above whatever
+// lo says (np.clip's order; lo <= hi is the caller's to keep).  LDS: 2048 x (8 + 4 + 4 x 4 + 4) B = 64 KB, two workgroups per CU; a tile
+// of GS_CELLS cells sums at most 2048 x 65535 < 2^27 in 32 bits.  The tiles' partials are added per gene by k_csr_gene_stats_parts_fold
+// into parts (6, G) int64 = [n_below, n_above, sum, sum of squares, positive counts, max]: what a cell-sharded caller adds (max: maximises)
+// over its ranks.  k_csr_gene_stats_clip then forms the four rows of vcy_gene_stats of the clipped values from them, the implicit and
+// stored zeros (z = n_cells - positive counts, each worth lo when lo > 0) included, in a fixed order with every product and sum rounded
+// on its own (no fma):  sum = (lo * (n_below + [lo > 0] z) + S1) + hi * n_above,  sum of squares = ((lo * lo) * (...) + S2) + (hi * hi) * n_above.
+// Integers in, one expression per gene out: the result does not depend on launch order, cell blocking or sharding.
+template <typename CT>
+__global__ __launch_bounds__(64 * GS_WAVES) void k_csr_gene_stats_parts(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                                         const CT *__restrict__ data, const int32_t *__restrict__ slabptr,
+                                                                         const uint8_t *__restrict__ cell_mask, const double *__restrict__ lo,
+                                                                         const double *__restrict__ hi, unsigned long long *__restrict__ p_sq,
+                                                                         unsigned *__restrict__ p_u32, int64_t C, int G, int nslab, int64_t tiles)
+{
+    __shared__ unsigned long long a_sq[GS_SLAB];
+    __shared__ unsigned a_sum[GS_SLAB], a_below[GS_SLAB], a_above[GS_SLAB], a_cnt[GS_SLAB], a_max[GS_SLAB], a_bnd[GS_SLAB];
+    const int64_t tile = blockIdx.x;
+    const int slab = blockIdx.y, g0 = slab * GS_SLAB;
+    for (int g = threadIdx.x; g < GS_SLAB; g += 64 * GS_WAVES) {
+        a_sq[g] = 0; a_sum[g] = 0; a_below[g] = 0; a_above[g] = 0; a_cnt[g] = 0; a_max[g] = 0;
+        unsigned jlo = 0u, ihi = 65535u;
+        if (lo && g0 + g < G) {
+            const double l = ceil(lo[g0 + g]) - 1.0, h = floor(hi[g0 + g]);
+            jlo = l >= 65535.0 ? 65535u : (l > 0.0 ? (unsigned)l : 0u);          // a NaN bound clips nothing
+            ihi = h >= 65535.0 ? 65535u : (h > 0.0 ? (unsigned)h : (h < 65535.0 ? 0u : 65535u));
+        }
+        a_bnd[g] = jlo | (ihi << 16);
+    }
+    __syncthreads();
+    const int64_t c0 = tile * GS_CELLS, c1 = min(C, c0 + GS_CELLS), nnz = indptr[C];
+    auto add = [&](unsigned g, unsigned x) {
+        if (x == 0u || g >= (unsigned)GS_SLAB) return;       // a stored zero is one of the gene's zeros; a gene outside the slab: a malformed table
+        const unsigned b = a_bnd[g];
+        atomicAdd(&a_cnt[g], 1u);
+        atomicMax(&a_max[g], x);
+        if (x > (b >> 16)) atomicAdd(&a_above[g], 1u);
+        else if (x <= (b & 0xffffu)) atomicAdd(&a_below[g], 1u);
+        else {
+            atomicAdd(&a_sum[g], x);
+            atomicAdd(&a_sq[g], (unsigned long long)x * x);
+        }
+    };
+    csr_slab_walk<CT, GS_WAVES, GS_ROWS, GS_NZ>(indptr, indices, data, slabptr, cell_mask, c0, c1, nnz, slab, nslab, g0, add);
+    __syncthreads();
+    const int64_t o = tile * G, plane = tiles * G;
+    for (int g = threadIdx.x; g < GS_SLAB && g0 + g < G; g += 64 * GS_WAVES) {
+        p_sq[o + g0 + g] = a_sq[g];
+        p_u32[o + g0 + g] = a_below[g];
+        p_u32[plane + o + g0 + g] = a_above[g];
+        p_u32[2 * plane + o + g0 + g] = a_sum[g];
+        p_u32[3 * plane + o + g0 + g] = a_cnt[g];
+        p_u32[4 * plane + o + g0 + g] = a_max[g];
+    }
+}
+
+// parts[:, g] = the tiles' partials of gene g added up (the maximum: maximised); the layout of k_csr_gene_stats_fold
+__global__ __launch_bounds__(64 * GS_FOLD) void k_csr_gene_stats_parts_fold(const unsigned long long *__restrict__ p_sq, const unsigned *__restrict__ p_u32,
+                                                                            long long *__restrict__ parts, int64_t tiles, int G)
+{
+    __shared__ unsigned long long r_v[GS_FOLD][6][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = blockIdx.x * 64 + lane;
+    const int64_t plane = tiles * G;
+    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};             // n_below, n_above, sum, sum of squares, positive counts, max
+    if (g < G)
+        for (int64_t t = wave; t < tiles; t += GS_FOLD) {
+            const int64_t o = t * G + g;
+            v[0] += p_u32[o];
+            v[1] += p_u32[plane + o];
+            v[2] += p_u32[2 * plane + o];
+            v[3] += p_sq[o];
+            v[4] += p_u32[3 * plane + o];
+            v[5] = max(v[5], (unsigned long long)p_u32[4 * plane + o]);
+        }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r_v[wave][k][lane] = v[k];
+    __syncthreads();
+    if (wave != 0 || g >= G) return;
+#pragma unroll
+    for (int w = 1; w < GS_FOLD; ++w) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v[k] += r_v[w][k][lane];
+        v[5] = max(v[5], r_v[w][5][lane]);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) parts[(int64_t)k * G + g] = (long long)v[k];
+}
+
+__global__ __launch_bounds__(256) void k_csr_gene_stats_clip(const long long *__restrict__ parts, const double *__restrict__ lo,
+                                                             const double *__restrict__ hi, double *__restrict__ stats, long long n_cells, int G)
+{
+#pragma clang fp contract(off)   // the order and the roundings above are the definition
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    const int64_t G64 = G;
+    const long long n_below = parts[g], n_above = parts[G64 + g], s1 = parts[2 * G64 + g], s2 = parts[3 * G64 + g], p = parts[4 * G64 + g];
+    const double mx = (double)parts[5 * G64 + g];
+    double s = (double)s1, ss = (double)(unsigned long long)s2, cnt = (double)p, m = mx;
+    if (lo && n_cells > 0) {
+        const double l = lo[g], h = hi[g];
+        const long long z = n_cells - p;
+        const double nb = (double)(n_below + (l > 0.0 ? z : 0)), na = (double)n_above;
+        s = (l * nb + s) + h * na;                                      // plain operators: the pragma above does not reach into __dmul_rn / __dadd_rn
+        ss = ((l * l) * nb + ss) + (h * h) * na;
+        cnt = h > 0.0 ? (double)(p + (l > 0.0 ? z : 0)) : 0.0;          // clip(x) > 0: every positive count when hi > 0, the zeros too when lo > 0
+        m = fmin(fmax(mx, l), h);                                       // clip is monotone: the largest clipped value is the clipped maximum
+    }
+    stats[g] = s;
+    stats[G64 + g] = ss;
+    stats[2 * G64 + g] = cnt;
+    stats[3 * G64 + g] = m;
 }
 
 // row_len[r] = number of stored elements of row r whose gene is kept
@@ -247,6 +323,58 @@ extern "C" int vcy_csr_gene_stats(const int64_t *indptr, const int32_t *indices,
     }
     hipLaunchKernelGGL(k_csr_gene_stats_fold, dim3((unsigned)((G + 63) / 64)), dim3(64 * GS_FOLD), 0, st, (const unsigned long long *)p_sum,
                        (const unsigned long long *)p_sq, (const unsigned *)p_cnt, (const unsigned *)p_max, stats, tiles, (int)G);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" size_t vcy_csr_gene_stats_parts_workspace_bytes(int64_t C, int64_t G)
+{
+    if (C <= 0 || G <= 0) return 0;
+    return (size_t)gs_tiles(C) * (size_t)G * (sizeof(unsigned long long) + 5 * sizeof(unsigned));
+}
+
+extern "C" int vcy_csr_gene_stats_parts(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *slabptr,
+                                        const uint8_t *cell_mask, const double *lo, const double *hi, int64_t *parts, void *workspace,
+                                        int64_t C, int64_t G, int count_dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(C >= 0 && G >= 0 && G < (1LL << 31), "csr_gene_stats_parts: bad shape (C >= 0, 0 <= G < 2^31)");
+    VCY_REQUIRE(count_dtype == VCY_U16 || count_dtype == VCY_U8, "csr_gene_stats_parts: count_dtype must be VCY_U16 or VCY_U8");
+    VCY_REQUIRE((lo == nullptr) == (hi == nullptr), "csr_gene_stats_parts: lo and hi go together");
+    if (G == 0) return VCY_OK;
+    VCY_REQUIRE(parts, "csr_gene_stats_parts: null pointer (parts)");
+    VCY_REQUIRE(C == 0 || (indptr && indices && data && slabptr && workspace), "csr_gene_stats_parts: null pointer");
+    VCY_REQUIRE(C == 0 || (uintptr_t)workspace % 8 == 0, "csr_gene_stats_parts: workspace must be 8-byte aligned");
+    VCY_REQUIRE(vcy_csr_slab_genes() == GS_SLAB, "csr_gene_stats_parts: slab size differs from vcy_csr_slab_genes()");
+    const int64_t tiles = gs_tiles(C), nslab = (G + GS_SLAB - 1) / GS_SLAB;
+    VCY_REQUIRE(tiles < (1LL << 31) && nslab < 65536, "csr_gene_stats_parts: grid too large");
+    hipStream_t st = as_stream(stream);
+    unsigned long long *p_sq = (unsigned long long *)workspace;
+    unsigned *p_u32 = (unsigned *)(p_sq + tiles * G);
+    if (tiles) {
+        const dim3 grid((unsigned)tiles, (unsigned)nslab);
+        if (count_dtype == VCY_U16)
+            hipLaunchKernelGGL(k_csr_gene_stats_parts<uint16_t>, grid, dim3(64 * GS_WAVES), 0, st, indptr, indices, (const uint16_t *)data, slabptr,
+                               cell_mask, lo, hi, p_sq, p_u32, C, (int)G, (int)nslab, tiles);
+        else
+            hipLaunchKernelGGL(k_csr_gene_stats_parts<uint8_t>, grid, dim3(64 * GS_WAVES), 0, st, indptr, indices, (const uint8_t *)data, slabptr,
+                               cell_mask, lo, hi, p_sq, p_u32, C, (int)G, (int)nslab, tiles);
+        VCY_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_csr_gene_stats_parts_fold, dim3((unsigned)((G + 63) / 64)), dim3(64 * GS_FOLD), 0, st, (const unsigned long long *)p_sq,
+                       (const unsigned *)p_u32, (long long *)parts, tiles, (int)G);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+extern "C" int vcy_csr_gene_stats_clip(const int64_t *parts, const double *lo, const double *hi, int64_t n_cells, double *stats, int64_t G,
+                                       vcy_stream stream)
+{
+    VCY_REQUIRE(G >= 0 && G < (1LL << 31) && n_cells >= 0, "csr_gene_stats_clip: bad shape (0 <= G < 2^31, n_cells >= 0)");
+    VCY_REQUIRE((lo == nullptr) == (hi == nullptr), "csr_gene_stats_clip: lo and hi go together");
+    if (G == 0) return VCY_OK;
+    VCY_REQUIRE(parts && stats, "csr_gene_stats_clip: null pointer");
+    hipLaunchKernelGGL(k_csr_gene_stats_clip, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, as_stream(stream), (const long long *)parts, lo, hi, stats,
+                       (long long)n_cells, (int)G);
     VCY_LAUNCH_CHECK();
     return VCY_OK;
 }

@@ -338,17 +338,7 @@ template <> struct Key<double> {
     static __device__ __forceinline__ double dec(U u) { u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u; return __longlong_as_double((long long)u); }
 };
 
-// numpy's _lerp between two order statistics a = v[lo], b = v[lo + 1] at fraction t, without fma contraction so that the rounding
-// matches numpy's mul-then-add; t == 0 returns a itself (also when b is infinite).  Shared by every percentile kernel of this file.
-__device__ __forceinline__ double lerp_numpy(double a, double b, double t)
-{
-#pragma clang fp contract(off)   // hipcc would fuse the mul/add below even through the *_rn intrinsics
-    const double diff = __dsub_rn(b, a);
-    double r = __dadd_rn(a, __dmul_rn(diff, t));
-    if (t >= 0.5) r = __dsub_rn(b, __dmul_rn(diff, __dsub_rn(1.0, t)));
-    if (t == 0.0) r = a;
-    return r;
-}
+// lerp_numpy (common.h): numpy's _lerp between two order statistics, shared by every percentile kernel of the library.
 
 // One histogram increment per matching lane.  Expression rows are mostly exact zeros and a row's values share a few exponents, so the
 // lanes of a wave mostly ask for the SAME bin - and LDS atomics on one address serialise, 64 deep when a whole wave holds zeros (the 2nd

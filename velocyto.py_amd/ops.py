@@ -416,18 +416,73 @@ def csr_select(counts: CsrCounts, remap, G_new: int) -> CsrCounts:
     return CsrCounts(ptr, idx, dat, G_new)
 
 
-def csr_gene_stats(counts: CsrCounts, cell_mask=None) -> torch.Tensor:
-    """(4, G) fp64 [sum, sum of squares, count(x > 0), max] per gene over the cells where cell_mask is true, straight from the cells-major
-    CSR layer (vcy_csr_gene_stats): the rows of gene_stats(counts.to_dense()), bit for bit, without the dense layer or the gene-major
-    copy.  Integer accumulation: independent of order and of how the cells are split.  Genes without a stored count give 0, 0, 0, 0."""
+def _csr_cell_mask(counts: CsrCounts, cell_mask) -> Optional[torch.Tensor]:
+    if cell_mask is None:
+        return None
+    mask = torch.as_tensor(cell_mask, device=counts.indptr.device).to(torch.uint8).contiguous()
+    if mask.numel() != counts.C:
+        raise ValueError(f"cell_mask needs one entry per cell: {mask.numel()} given, C = {counts.C}")
+    return mask
+
+
+def _gene_bounds(lo, hi, G: int, dev) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    if (lo is None) != (hi is None):
+        raise ValueError("lo and hi go together")
+    if lo is None:
+        return None, None
+    lo, hi = (torch.as_tensor(v, device=dev).to(torch.float64).contiguous().reshape(-1) for v in (lo, hi))
+    if lo.numel() != G or hi.numel() != G:
+        raise ValueError(f"lo and hi need one entry per gene: {lo.numel()} and {hi.numel()} given, G = {G}")
+    return lo, hi
+
+
+def csr_gene_stats_parts(counts: CsrCounts, cell_mask=None, lo=None, hi=None) -> torch.Tensor:
+    """(6, G) int64 [positive counts < lo, counts > hi, sum and sum of squares of the other positive counts, number of positive counts,
+    largest count] per gene over the cells where cell_mask is true (vcy_csr_gene_stats_parts): the integer parts of the statistics of
+    the counts clipped to [lo, hi], before csr_gene_stats_clip folds them.  A cell-sharded caller adds rows 0-4 and maximises row 5
+    over its ranks first.  lo = hi = None: nothing is clipped."""
     L = _lib.lib()
     dev = counts.indptr.device
     C, G = counts.C, counts.G
-    mask = None
-    if cell_mask is not None:
-        mask = torch.as_tensor(cell_mask, device=dev).to(torch.uint8).contiguous()
-        if mask.numel() != C:
-            raise ValueError(f"cell_mask needs one entry per cell: {mask.numel()} given, C = {C}")
+    mask = _csr_cell_mask(counts, cell_mask)
+    lo, hi = _gene_bounds(lo, hi, G, dev)
+    parts = torch.empty((6, G), dtype=torch.int64, device=dev)
+    if G == 0:
+        return parts
+    n = int(L.vcy_csr_gene_stats_parts_workspace_bytes(C, G))
+    ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=dev) if n else None
+    _lib.check(L.vcy_csr_gene_stats_parts(counts.indptr.data_ptr(), counts._istore.data_ptr(), counts._dstore.data_ptr(), counts.slabptr.data_ptr(),
+                                          _p(mask), _p(lo), _p(hi), parts.data_ptr(), _p(ws), C, G, counts.code, _stream()), "csr_gene_stats_parts")
+    return parts
+
+
+def csr_gene_stats_clip(parts: torch.Tensor, n_cells: int, lo=None, hi=None) -> torch.Tensor:
+    """(4, G) fp64 [sum, sum of squares, count(> 0), max] of the counts clipped to [lo, hi] over n_cells cells - the zeros included -
+    from the integer parts of csr_gene_stats_parts, summed over every rank (vcy_csr_gene_stats_clip: one fixed expression per gene)."""
+    G = int(parts.shape[1])
+    dev = parts.device
+    if parts.dtype != torch.int64 or parts.shape[0] != 6:
+        raise ValueError(f"csr_gene_stats_clip: parts must be (6, G) int64, got {tuple(parts.shape)} {parts.dtype}")
+    lo, hi = _gene_bounds(lo, hi, G, dev)
+    parts = parts.contiguous()
+    out = torch.empty((4, G), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().vcy_csr_gene_stats_clip(parts.data_ptr(), _p(lo), _p(hi), int(n_cells), out.data_ptr(), G, _stream()), "csr_gene_stats_clip")
+    return out
+
+
+def csr_gene_stats(counts: CsrCounts, cell_mask=None, lo=None, hi=None) -> torch.Tensor:
+    """(4, G) fp64 [sum, sum of squares, count(x > 0), max] per gene over the cells where cell_mask is true, straight from the cells-major
+    CSR layer (vcy_csr_gene_stats): the rows of gene_stats(counts.to_dense()), bit for bit, without the dense layer or the gene-major
+    copy.  Integer accumulation: independent of order and of how the cells are split.  Genes without a stored count give 0, 0, 0, 0.
+    lo, hi (per gene, both or neither): the statistics of the counts clipped to [lo, hi] - the rows of gene_stats(dense, lo=, hi=,
+    cell_mask=) - as csr_gene_stats_clip(csr_gene_stats_parts(...)) forms them from integers."""
+    L = _lib.lib()
+    dev = counts.indptr.device
+    C, G = counts.C, counts.G
+    mask = _csr_cell_mask(counts, cell_mask)
+    if lo is not None or hi is not None:
+        n_cells = C if mask is None else int((mask != 0).sum())
+        return csr_gene_stats_clip(csr_gene_stats_parts(counts, mask, lo, hi), n_cells, lo, hi)
     out = torch.empty((4, G), dtype=torch.float64, device=dev)
     if G == 0:
         return out
@@ -436,6 +491,100 @@ def csr_gene_stats(counts: CsrCounts, cell_mask=None) -> torch.Tensor:
     _lib.check(L.vcy_csr_gene_stats(counts.indptr.data_ptr(), counts._istore.data_ptr(), counts._dstore.data_ptr(), counts.slabptr.data_ptr(),
                                     _p(mask), out.data_ptr(), _p(ws), C, G, counts.code, _stream()), "csr_gene_stats")
     return out
+
+
+class CsrGeneQuantiles:
+    """np.percentile(dense, qs, axis=cells) of a cells-major CSR count layer over n_total selected cells, implicit zeros included, exact,
+    from the layer as it is (vcy_csr_quantiles_*: a radix select on 8-bit digits over the positive stored counts; one walk over a
+    uint8 layer, two over uint16).  One pass = add_block() on EVERY block of cells (any order, any blocking; the cells of all ranks in
+    a cell-sharded run - every block of the same `wide`-ness), then advance(), which adds the integer histograms over the ranks; when
+    `done`, result() is the (len(qs), G) float64 tensor.  A caller that moves the counts between its pieces itself adds their
+    `pass_hist` and `cells_in_pass`, gives every piece the sums, and then lets each advance.  n_total: the selected cells of all
+    blocks together (masked-out cells do not count).  wide: uint16 counts (int16 storage) rather than uint8."""
+
+    def __init__(self, G: int, qs: Sequence[float], n_total: int, wide: bool, device=None):
+        self.G, self.n_total, self.wide = int(G), int(n_total), bool(wide)
+        if self.n_total < 1:
+            raise ValueError("CsrGeneQuantiles: no cell is selected (n_total must be at least 1)")
+        self.ranks, self._lo, self._hi, self._t = percentile_targets(qs, self.n_total)
+        self.nq, self.nt = len(self._lo), len(self.ranks)
+        self.code = U16 if self.wide else U8
+        self.dev = require_gpu() if device is None else torch.device(device)
+        L = _lib.lib()
+        self.passes = int(L.vcy_csr_quantiles_passes(self.code))
+        self.state = torch.empty(int(L.vcy_csr_quantiles_state_bytes(self.G, self.nt)) // 4, dtype=torch.int32, device=self.dev)
+        # int32 (the counters are uint32 and never exceed n_total < 2^31): the type the histograms are summed in over the ranks
+        self.hist = torch.empty((1 + (self.nt if self.wide else 0), self.G, 256), dtype=torch.int32, device=self.dev)
+        assert self.hist.numel() * 4 == int(L.vcy_csr_quantiles_hist_bytes(self.G, self.nt, self.code))
+        _lib.check(L.vcy_csr_quantiles_begin(self.hist.data_ptr(), self.nt, self.G, self.code, _stream()), "csr_quantiles_begin")
+        self.pass_no = 0
+        self.cells_in_pass = 0          # selected cells this rank added in the current pass
+
+    @property
+    def done(self) -> bool:
+        return self.pass_no >= self.passes
+
+    @property
+    def pass_hist(self) -> torch.Tensor:
+        """The integer histograms the current pass counts into (a view): what is added over the pieces before advance()."""
+        return self.hist[:1] if self.pass_no == 0 else self.hist[1:]          # after pass 0, hist[0] is a table, not counts
+
+    @property
+    def state_bytes(self) -> int:
+        return self.state.numel() * 4 + self.hist.numel() * 4
+
+    def add_block(self, counts: CsrCounts, cell_mask=None) -> None:
+        if self.done:
+            raise RuntimeError("CsrGeneQuantiles.add_block: every pass is done")
+        if counts.G != self.G or counts.code != self.code:
+            raise ValueError(f"CsrGeneQuantiles.add_block: a block of {counts.G} genes, {'uint16' if counts.code == U16 else 'uint8'} counts for a "
+                             f"select over {self.G} genes, {'uint16' if self.wide else 'uint8'} counts")
+        mask = _csr_cell_mask(counts, cell_mask)
+        if counts.C == 0:
+            return
+        _lib.check(_lib.lib().vcy_csr_quantiles_count(counts.indptr.data_ptr(), counts._istore.data_ptr(), counts._dstore.data_ptr(),
+                                                      counts.slabptr.data_ptr(), _p(mask), self.hist.data_ptr(), self.pass_no, self.nt, counts.C,
+                                                      self.G, self.code, _stream()), "csr_quantiles_count")
+        self.cells_in_pass += counts.C if mask is None else int((mask != 0).sum())
+
+    def advance(self, group=None) -> None:
+        """Ends a pass: sums the integer histograms (and the selected cells) over the ranks, then fixes the next digit of every target."""
+        from . import distributed as D
+        if self.done:
+            raise RuntimeError("CsrGeneQuantiles.advance: every pass is done")
+        cells = self.cells_in_pass
+        if D.active():
+            cells = int(D.all_reduce_sum(torch.tensor([cells], dtype=torch.int64, device=self.dev), group).item())
+            D.all_reduce_sum(self.pass_hist, group)
+        if cells != self.n_total:
+            raise ValueError(f"CsrGeneQuantiles.advance: the pass saw {cells} selected cells, the select was set up for n_total = {self.n_total}")
+        _lib.check(_lib.lib().vcy_csr_quantiles_advance(self.state.data_ptr(), self.hist.data_ptr(), (ctypes.c_int64 * self.nt)(*self.ranks), self.pass_no,
+                                                        self.nt, self.n_total, self.G, self.code, _stream()), "csr_quantiles_advance")
+        self.pass_no += 1
+        self.cells_in_pass = 0
+
+    def result(self) -> torch.Tensor:
+        if not self.done:
+            raise RuntimeError(f"CsrGeneQuantiles.result: {self.pass_no} of {self.passes} passes done")
+        out = torch.empty((self.nq, self.G), dtype=torch.float64, device=self.dev)
+        lo, hi, t = (ctypes.c_int * self.nq)(*self._lo), (ctypes.c_int * self.nq)(*self._hi), (ctypes.c_double * self.nq)(*self._t)
+        _lib.check(_lib.lib().vcy_csr_quantiles_finish(self.state.data_ptr(), lo, hi, t, self.nq, self.nt, out.data_ptr(), self.G, _stream()),
+                   "csr_quantiles_finish")
+        return out
+
+
+def csr_gene_quantiles(counts: CsrCounts, qs: Sequence[float], cell_mask=None) -> torch.Tensor:
+    """np.percentile(counts.to_dense(), qs, axis=cells) -> (len(qs), G) float64 over the cells where cell_mask is true, bit for bit and
+    bit for bit what gene_quantiles gives on the dense float layer, without that layer (CsrGeneQuantiles in one call)."""
+    mask = _csr_cell_mask(counts, cell_mask)
+    n = counts.C if mask is None else int((mask != 0).sum())
+    if n == 0:
+        raise ValueError("csr_gene_quantiles: no cell is selected")
+    sel = CsrGeneQuantiles(counts.G, qs, n, counts.code == U16, counts.indptr.device)
+    while not sel.done:
+        sel.add_block(counts, mask)
+        sel.advance()
+    return sel.result()
 
 
 # --------------------------------------------------------------------------- .loom ingest in blocks of cells (csrc/ingest.hip)
