@@ -452,6 +452,17 @@ int vcy_fit_weighted_moments_masked(const void *Y, const void *X, int weight_mod
                                     const double *scale_a, const double *scale_b, const double *down, const double *up,
                                     const unsigned char *cell_mask, double *moments, void *workspace, int64_t C, int64_t G,
                                     int64_t ld, int dtype, vcy_stream stream);
+/* vcy_fit_weighted_moments with the weight of vcy_gamma_weights formed inside the fold, for blocks that cannot afford the dense W:
+ * fused_mode and S, U, pa, pb, pc, pd, sa, sb, power are vcy_gamma_weights' mode (0 "sum", 1 "prod", 2 "maxmin_weighted",
+ * 3 "maxmin_double") and arguments.  The weight of element (c, g) is evaluated in double, rounded to `dtype` - the value the
+ * dense W would store - and widened again: the (10, G) moments are bit for bit those of vcy_gamma_weights followed by
+ * vcy_fit_weighted_moments[_masked](weight_mode 0), in the same fixed block order.  cell_mask: uint8 (C), device, or NULL = all
+ * cells (a masked-out row adds nothing and is not read; all ones = NULL bit for bit).  "maxmin" / "maxmin_diag" are weight_mode 1
+ * and the unweighted fit weight_mode 2 of vcy_fit_weighted_moments.  workspace: vcy_fit_workspace_bytes(G).                     */
+int vcy_fit_weighted_moments_fused(const void *Y, const void *X, int fused_mode, const void *S, const void *U, const double *pa,
+                                   const double *pb, const double *pc, const double *pd, const double *sa, const double *sb,
+                                   double power, const unsigned char *cell_mask, double *moments, void *workspace, int64_t C,
+                                   int64_t G, int64_t ld, int dtype, vcy_stream stream);
 int vcy_fit_weighted_from_moments(const double *moments, int64_t n_cells, int fit_offset, int box_q, double lo_gamma,
                                   double up_gamma_default, const double *up_gamma, const double *q_fixed, float *gamma, float *q,
                                   float *R2, int64_t G, vcy_stream stream);

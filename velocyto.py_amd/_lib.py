@@ -171,6 +171,8 @@ SIGNATURES = {
     "vcy_fit_weighted_moments": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     "vcy_fit_weighted_moments_masked": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                                 c_int, c_vp]),
+    "vcy_fit_weighted_moments_fused": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                               c_i64, c_int, c_vp]),
     "vcy_fit_weighted_from_moments": (c_int, [c_vp, c_i64, c_int, c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "vcy_gene_slices_pack": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     "vcy_gene_slices_unpack": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),

@@ -36,6 +36,7 @@ import torch.distributed as dist
 
 from . import distributed as D
 from . import ops
+from .streamed_fit import StreamedFit, check_weights
 
 KEY_CHUNK = 4096          # cells per deterministic block of the synthetic generator and of the sampling keys
 PRUNE_FROM = 100_000      # cells from which the kNN search in the PCA space is projection-pruned (AtlasPath(knn="auto"))
@@ -87,7 +88,8 @@ class AtlasPath:
                  sampling_probs=(0.5, 0.1), block_cells: int = 0, dtype=torch.float32, psc: float = 1e-10, seed: int = 15071990,
                  knn: str = "auto", fit: str = "slope", shift: bool = False, sigma_corr: float = 0.05, expression_scaling: bool = True,
                  scaling_penalty: float = 1.0, balanced: bool = False, b_sight: Optional[int] = None, b_maxl: Optional[int] = None,
-                 group_constraint=None, fit_offset: bool = True, fixperc_q: bool = False, limit_gamma: bool = False, steady_state_bool=None):
+                 group_constraint=None, fit_offset: bool = True, fixperc_q: bool = False, limit_gamma: bool = False, steady_state_bool=None,
+                 weighted: bool = True, weights="maxmin_diag", maxmin_perc=(2, 98), maxmin_weighted_pow: float = 15):
         """fit: how stage B fits gamma.  "slope" (the default): gamma = max(0, sum xy / sum xx), unweighted, no offset (fit_slope,
         estimation.py:267-279).  "maxmin_diag" (or "default"): velocyto's default fit_gammas(weights="maxmin_diag", fit_offset=True)
         (analysis.py:1179-1257), the recipe of VelocytoLoom.fit_gammas and ShardedLoom.fit_gammas, with the per-gene percentiles
@@ -102,6 +104,11 @@ class AtlasPath:
         cells only.  Their conditional percentiles come from the masked streamed select (ops.StreamedMaskedGeneQuantiles) in the
         walks the default fit already makes: the number of walks does not change.  With none of the four given the run is bit for
         bit the default fit's.
+        weighted, weights, maxmin_perc, maxmin_weighted_pow (fit="maxmin_diag" only, like the four above): VelocytoLoom.fit_gammas'
+        arguments of these names - weights one of "sum", "prod", "maxmin", "maxmin_weighted", "maxmin_diag", "maxmin_double" (anything
+        else is the facade's ValueError; the weight mode never travels in fit=), or weighted=False.  The walk plan per mode is
+        streamed_fit.StreamedFit's; the non-binary weights are formed inside the moments fold (ops.fit_weighted_moments_fused), never
+        as a block-sized matrix.  With the defaults the run is bit for bit the default fit's.
         shift: also calculate_embedding_shift (analysis.py:1670-1733, stage E) with sigma_corr, expression_scaling and scaling_penalty
         as there, block by block while the block is in the staging buffers: run() then leaves tp, delta_embedding, scaling and
         delta_embedding_unscaled of the rank's own cells (see _stage_e); delta_S is never formed.
@@ -115,9 +122,16 @@ class AtlasPath:
             raise ValueError(f"AtlasPath: unknown fit={fit!r} (\"slope\", \"maxmin_diag\" or \"default\")")
         self.fit = "slope" if fit == "slope" else "maxmin_diag"
         self.fit_offset, self.fixperc_q, self.limit_gamma = bool(fit_offset), bool(fixperc_q), bool(limit_gamma)
-        if self.fit == "slope" and (not self.fit_offset or self.fixperc_q or self.limit_gamma or steady_state_bool is not None):
-            raise ValueError("AtlasPath: fit_offset, fixperc_q, limit_gamma and steady_state_bool belong to fit=\"maxmin_diag\"; "
-                             "fit=\"slope\" has no offset, no weights and no steady-state cells")
+        self.weighted, self.weights, self.maxmin_weighted_pow = bool(weighted), weights, float(maxmin_weighted_pow)
+        self.maxmin_perc = tuple(float(p) for p in maxmin_perc)
+        other_weights = (not self.weighted or not (isinstance(weights, str) and weights == "maxmin_diag") or self.maxmin_perc != (2.0, 98.0)
+                         or self.maxmin_weighted_pow != 15.0)
+        if self.fit == "slope" and (not self.fit_offset or self.fixperc_q or self.limit_gamma or steady_state_bool is not None or other_weights):
+            raise ValueError("AtlasPath: fit_offset, fixperc_q, limit_gamma and steady_state_bool belong to fit=\"maxmin_diag\", and so do "
+                             "weighted, weights, maxmin_perc and maxmin_weighted_pow; fit=\"slope\" has no offset, no weights and no "
+                             "steady-state cells")
+        if self.weighted:
+            check_weights(weights)
         self.dev = dev = cS.indptr.device
         self.knn_mode = knn
         self.dtype = ops.resolve_dtype(dtype)
@@ -184,7 +198,8 @@ class AtlasPath:
         self.corr = torch.empty((self.nloc, self.nrndm), dtype=self.dtype, device=dev)
         self.gamma = None
         self.q = self.R2 = None            # fit="maxmin_diag": the offset and the weighted R2 of the fit (float32, like gamma)
-        self.fit_thresholds = None         # ... and its per-gene float64 thresholds {"denom_S", "denom_U", "down", "up"}; with
+        self.fit_thresholds = None         # ... and its per-gene float64 thresholds {"denom_S", "denom_U", "down", "up"} (other weights:
+        #     see streamed_fit.StreamedFit - "sum"/"prod" {"p99_S", "p99_U"}, "maxmin"/"maxmin_weighted" {"down_S", "up_S"}, "maxmin_double" both); with
         #     limit_gamma also {"med_S", "p90_S", "med_U", "U_p10_above", "S_med_above", "n_above" (int64: cells with Sx > p90_S),
         #     "up_gamma"}, with fixperc_q {"p1_S", "n_below" (int64: cells with Sx <= p1_S), "q_fixed"} - over the steady-state cells
         self.fit_moments = None            # ... and the all-reduced (10, G) moments they were solved from
@@ -351,122 +366,40 @@ class AtlasPath:
                 tms[0 if i_pass == 0 else 1] += ev[0].elapsed_time(ev[1]); tms[1] += ev[1].elapsed_time(ev[2])
 
     def _fit_maxmin_diag(self, ev, timed: bool, tms: List[float]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """fit_gammas(weights="maxmin_diag", fit_offset=True) (analysis.py:1179-1257) over blocks, in three phases of walks:
-        (1) percentiles [99.9, 100] of Sx and of Ux -> the denominators of VelocytoLoom._maxnorm_denominator; (2) percentiles
-        [2, 98] of Sx/dS + Ux/dU -> the binary weights' thresholds; (3) the weighted moments, all-reduced and solved in the box
-        (the recipe of ShardedLoom.fit_gammas).  Phases 1 and 2 take one walk per 8-bit digit of the key each.
-        limit_gamma / fixperc_q ride on the same walks (masked selects over the steady-state cells): the unconditional percentiles
-        ([50, 90] or [1] of Sx, [50] of Ux) in phase 1, the conditional ones, which need only those, in phase 2 beside [2, 98]."""
-        G, C = self.G, self.C
+        """fit_gammas (analysis.py:1179-1257) over blocks: the walks of streamed_fit.StreamedFit, fed from the staging buffers.  With the
+        default weights="maxmin_diag" three phases: (1) percentiles [99.9, 100] of Sx and of Ux -> the denominators of
+        VelocytoLoom._maxnorm_denominator; (2) percentiles [2, 98] of Sx/dS + Ux/dU -> the binary weights' thresholds; (3) the weighted
+        moments, all-reduced and solved in the box.  Phases 1 and 2 take one walk per 8-bit digit of the key each; limit_gamma /
+        fixperc_q ride on the same walks (masked selects over the steady-state cells).  The other weight modes: StreamedFit's plan."""
         facts = {"abs_st": None, "absmax": None}
-        selS = ops.StreamedGeneQuantiles(G, [99.9, 100], C, self.dtype, self.dev)
-        selU = ops.StreamedGeneQuantiles(G, [99.9, 100], C, self.dtype, self.dev)
-        need_up = self.limit_gamma and (self.fit_offset or not self.fixperc_q)
-        need_qf = self.fixperc_q and not self.fit_offset
+        fit = StreamedFit(self.G, self.C, self.dtype, self.dev, weighted=self.weighted, weights=self.weights, fit_offset=self.fit_offset,
+                          fixperc_q=self.fixperc_q, limit_gamma=self.limit_gamma, maxmin_perc=self.maxmin_perc,
+                          maxmin_weighted_pow=self.maxmin_weighted_pow, n_fit_cells=self.n_fit_cells)
         cmask = lambda: None if self._ss is None else self._ss[self._blk[0]:self._blk[1]]      # of the block being used
-        msel = lambda qs: ops.StreamedMaskedGeneQuantiles(G, qs, self.dtype, self.dev)
-        xS = msel([50, 90]) if need_up else (msel([1]) if need_qf else None)                  # phase 1 extras: of Sx ...
-        xU = msel([50]) if need_up else None                                                   # ... and of Ux
-        extra = [x for x in (xS, xU) if x is not None]
-        self.select_state_bytes = selS.state_bytes + selU.state_bytes + sum(x.state_bytes for x in extra)
-        n_passes = 2 * selS.passes + 1
-        i_pass = 0
 
-        def end_pass(*sels):
+        def timed_(f):
             ev[0].record()
-            for sel in sels:
-                sel.advance()
+            out = f()
             ev[1].record()
             if timed:
                 torch.cuda.synchronize()
                 tms[1] += ev[0].elapsed_time(ev[1])
+            return out
 
-        while not selS.done:
+        for i_pass in range(fit.n_walks):
             first = i_pass == 0 and self.rules is None
 
             def use(Sx_b, Ux_b):
-                selS.add_block(Sx_b)
-                selU.add_block(Ux_b)
-                if xS is not None:
-                    xS.add_block(Sx_b, cell_mask=cmask())
-                if xU is not None:
-                    xU.add_block(Ux_b, cell_mask=cmask())
+                fit.add_block(Sx_b, Ux_b, cell_mask=cmask())
                 if first:
                     self._gather_facts(Sx_b, facts)
-            self._data_pass(i_pass, n_passes, use, ev, timed, tms)
+            self._data_pass(i_pass, fit.n_walks, use, ev, timed, tms)
             if first:
                 self._decide_rules(facts)
-            end_pass(selS, selU, *extra)
-            i_pass += 1
-        ev[0].record()
-        denom = lambda p: torch.where(p[0] == 0, torch.clamp(p[1], min=0.001), p[0]).contiguous()     # _maxnorm_denominator's rule
-        dS, dU = denom(selS.result()), denom(selU.result())
-        del selS, selU
-        selZ = ops.StreamedGeneQuantiles(G, [2, 98], C, self.dtype, self.dev, two=True)
-        opt = {}                           # what limit_gamma / fixperc_q add to fit_thresholds
-        cond = []                          # phase 2 extras: (select, its matrix is Ux (else Sx), threshold, mask_mode)
-        if need_up:
-            qx = xS.result()
-            opt.update(med_S=qx[0].contiguous(), p90_S=qx[1].contiguous(), med_U=xU.result()[0].contiguous())
-            cond = [(msel([10]), True, opt["p90_S"], 1), (msel([50]), False, opt["p90_S"], 1)]     # y[x > p90] at 10, x[x > p90] at 50
-        elif need_qf:
-            opt.update(p1_S=xS.result()[0].contiguous())
-            cond = [(msel([50]), True, opt["p1_S"], 2)]                                           # y[x <= p1] at 50
-        del xS, xU, extra
-        self.select_state_bytes = max(self.select_state_bytes, selZ.state_bytes + sum(c[0].state_bytes for c in cond))
-        ev[1].record()
-        if timed:
-            torch.cuda.synchronize()
-            tms[1] += ev[0].elapsed_time(ev[1])
-
-        def use_z(Sx_b, Ux_b):
-            selZ.add_block(Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU)
-            for sel, of_u, thr, mode in cond:
-                sel.add_block(Ux_b if of_u else Sx_b, mask_src=Sx_b, mask_thr=thr, mask_mode=mode, cell_mask=cmask())
-        while not selZ.done:
-            self._data_pass(i_pass, n_passes, use_z, ev, timed, tms)
-            end_pass(selZ, *[c[0] for c in cond])
-            i_pass += 1
-        th = selZ.result()
-        down, up = th[0].contiguous(), th[1].contiguous()
-        del selZ
-        self.fit_thresholds = {"denom_S": dS, "denom_U": dU, "down": down, "up": up}
-        up_gamma = q_fixed = None
-        if need_up:                        # estimation._median_and_up_gamma from the streamed percentiles
-            y10, xm = cond[0][0].result()[0], cond[1][0].result()[0]
-            upg = torch.maximum(torch.full_like(y10, 1.5), y10 / xm)
-            up_gamma = torch.where(opt["med_U"] > opt["med_S"], upg, torch.full_like(upg, 1.5))
-            opt.update(U_p10_above=y10, S_med_above=xm, n_above=cond[0][0].counts(), up_gamma=up_gamma)
-        elif need_qf:                      # estimation._fixperc_q
-            q_fixed = cond[0][0].result()[0]
-            opt.update(n_below=cond[0][0].counts(), q_fixed=q_fixed)
-        self.fit_thresholds.update(opt)
-        del cond
-        moms = []
-
-        def use(Sx_b, Ux_b):
-            m = ops.fit_weighted_moments(Ux_b, Sx_b, 1, M=Sx_b, M2=Ux_b, scale_a=dS, scale_b=dU, down=down, up=up, cell_mask=cmask())
-            moms[:] = [m if not moms else moms[0].add_(m)]
-        self._data_pass(i_pass, n_passes, use, ev, timed, tms)
-        ev[0].record()
-        mom = moms[0] if moms else torch.zeros((10, G), dtype=torch.float64, device=self.dev)
-        D.all_reduce_sum(mom)
-        self.fit_moments = mom
-        n = self.n_fit_cells
-        if self.fit_offset:                # the arguments of estimation._weighted_offset_device / VelocytoLoom.fit_gammas per branch
-            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=True, box_q=True, lo_gamma=1e-8, up_gamma_default=20.0, up_gamma=up_gamma)
-        elif need_qf:
-            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=False, lo_gamma=0.0, up_gamma_default=20.0, q_fixed=q_fixed)
-        elif need_up:
-            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=False, lo_gamma=1e-8, up_gamma=up_gamma)
-        else:
-            gamma, q, R2 = ops.fit_weighted_from_moments(mom, n, fit_offset=False, lo_gamma=0.0, up_gamma_default=20.0)
-        gamma = torch.where(torch.isfinite(gamma), gamma, torch.zeros_like(gamma))                    # analysis.py:1260
+            timed_(fit.end_walk)
+        gamma, q, R2 = timed_(fit.result)
+        self.fit_thresholds, self.fit_moments, self.select_state_bytes = fit.thresholds, fit.moments, fit.state_bytes
         self.q, self.R2 = q, R2
-        ev[1].record()
-        if timed:
-            torch.cuda.synchronize()
-            tms[1] += ev[0].elapsed_time(ev[1])
         return gamma, q
 
     # ------------------------------------------------------------------ stage E of one block

@@ -183,6 +183,29 @@ __device__ __forceinline__ double lerp_numpy(double a, double b, double t)
     return r;
 }
 
+// One element of fit_gammas' non-binary weights (analysis.py:1182-1192, 1208-1219; the modes of vcy_gamma_weights), from the stored
+// values s, u of the cell and the gene's fp64 thresholds: evaluated in double, rounded to T - the value the dense W of
+// vcy_gamma_weights stores.  Shared by k_gamma_weights (misc.hip) and the fused moments fold (fit.hip), which widens it again, so
+// the two routes sum bit-identical weights.  sa, sb (mode 3 only) are the denominators already rounded to T: Z is formed in T,
+// like k_build_z forms it.  u is not read in mode 2, pc / pd / sa / sb only in mode 3.
+// Contraction is off for the operations written here: in f64 the rounding to T is no operation, and the fold would otherwise fuse
+// the last product ("prod"'s, or the 0.5 of "maxmin_weighted") into its own sums - a weight the dense W never held.
+template <typename T>
+__device__ __forceinline__ T gamma_weight_element(int mode, T s, T u, double pa, double pb, double pc, double pd, T sa, T sb, double pw)
+{
+#pragma clang fp contract(off)
+    const double sd = (double)s;
+    if (mode == 0) return (T)(sd / pa + (double)u / pb);
+    if (mode == 1) return (T)((sd / pa) * ((double)u / pb));
+    if (mode == 2) {
+        const double lo = pa, hi = pb;
+        const double r = (fmin(fmax(sd, lo), hi) - lo) / (hi - lo);
+        return (T)(0.5 * (pow(r, pw) + pow(1.0 - r, pw)));
+    }
+    const double z = (double)(T)(s / sa + u / sb);
+    return (T)(((z <= pa || z >= pb) ? 1.0 : 0.0) + ((sd <= pc || sd >= pd) ? 1.0 : 0.0));
+}
+
 inline hipStream_t as_stream(vcy_stream s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- process-wide facts, each computed once under a lock and then only read (layout.hip): nothing a call can observe

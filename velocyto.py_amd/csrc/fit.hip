@@ -110,13 +110,18 @@ template <typename T> __device__ __forceinline__ T zvalue(T m, T m2, T a, T b, b
 
 // CM: cells with cmask[c] == 0 add nothing and are not read (the steady-state cells of fit_gammas); the kept cells are summed in
 // the order the unmasked kernel sums them, so an all-ones mask gives its moments bit for bit.
+// WMODE 3..6: the fused weights, gamma_weight_element's modes 0..3 ("sum", "prod", "maxmin_weighted", "maxmin_double") evaluated in
+// the fold - no dense W.  The arguments then carry that function's: M = S, M2 = U (not read in mode 2), down = pa, up = pb,
+// scale_a = sa, scale_b = sb, and pc, pd, pw.
+constexpr int WMODE_FUSED = 3;
 template <typename T, int WMODE, bool CM>
 __device__ __forceinline__ void moments_weighted_body(const T *__restrict__ Y, const T *__restrict__ X, const T *__restrict__ W,
                                                       const T *__restrict__ M, const T *__restrict__ M2,
                                                       const double *__restrict__ scale_a, const double *__restrict__ scale_b,
                                                       const double *__restrict__ down, const double *__restrict__ up,
                                                       double *__restrict__ part, int C, int G, int64_t ld,
-                                                      const unsigned char *__restrict__ cmask)
+                                                      const unsigned char *__restrict__ cmask, const double *__restrict__ pc = nullptr,
+                                                      const double *__restrict__ pd = nullptr, double pw = 0.0)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;   // lane <-> gene: coalesced 4/8-byte row segments
     if (g >= G) return;
@@ -130,6 +135,12 @@ __device__ __forceinline__ void moments_weighted_body(const T *__restrict__ Y, c
         if (two) { den_a = (T)scale_a[g]; den_b = (T)scale_b[g]; }
         dn = down[g]; upv = up[g];
     }
+    constexpr int FM = WMODE - WMODE_FUSED;      // the fused weight's mode and its per-gene values
+    double fpc = 0, fpd = 0;
+    if (WMODE >= WMODE_FUSED) {
+        dn = down[g]; upv = up[g];
+        if (FM == 3) { fpc = pc[g]; fpd = pd[g]; den_a = (T)scale_a[g]; den_b = (T)scale_b[g]; }
+    }
     double sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0, sw = 0, swx = 0, swy = 0, swxx = 0, swxy = 0;
 #pragma unroll 4
     for (int c = c0; c < c1; ++c) {
@@ -141,6 +152,8 @@ __device__ __forceinline__ void moments_weighted_body(const T *__restrict__ Y, c
         else if (WMODE == 1) {
             const double z = (double)zvalue<T>(M[o], two ? M2[o] : T(0), den_a, den_b, two);
             w = (z <= dn || z >= upv) ? 1.0 : 0.0;
+        } else if (WMODE >= WMODE_FUSED) {
+            w = (double)gamma_weight_element<T>(FM, M[o], FM != 2 ? M2[o] : T(0), dn, upv, fpc, fpd, den_a, den_b, pw);
         } else w = 1.0;
         sx += x; sy += y; sxx = fma(x, x, sxx); sxy = fma(x, y, sxy); syy = fma(y, y, syy);
         const double wx = w * x;
@@ -171,6 +184,17 @@ __global__ __launch_bounds__(256) void k_moments_weighted_masked(const T *__rest
                                                                   const unsigned char *__restrict__ cmask)
 {
     moments_weighted_body<T, WMODE, true>(Y, X, W, M, M2, scale_a, scale_b, down, up, part, C, G, ld, cmask);
+}
+
+template <typename T, int FM, bool CM>
+__global__ __launch_bounds__(256) void k_moments_fused(const T *__restrict__ Y, const T *__restrict__ X, const T *__restrict__ S,
+                                                        const T *__restrict__ U, const double *__restrict__ pa, const double *__restrict__ pb,
+                                                        const double *__restrict__ pc, const double *__restrict__ pd,
+                                                        const double *__restrict__ sa, const double *__restrict__ sb, double pw,
+                                                        double *__restrict__ part, int C, int G, int64_t ld,
+                                                        const unsigned char *__restrict__ cmask)
+{
+    moments_weighted_body<T, WMODE_FUSED + FM, CM>(Y, X, nullptr, S, U, sa, sb, pa, pb, part, C, G, ld, cmask, pc, pd, pw);
 }
 
 // Exact minimiser of  sum w (x m + q - y)^2  over [lo_m,hi_m] x [lo_q,hi_q] from the weighted
@@ -951,6 +975,41 @@ extern "C" int vcy_fit_weighted_moments_masked(const void *Y, const void *X, int
     hipStream_t st = as_stream(stream);
     int rc = fit_weighted_partials(Y, X, weight_mode, W, M, M2, scale_a, scale_b, down, up, workspace, C, G, ld, dtype, st, cell_mask);
     if (rc) return rc;
+    hipLaunchKernelGGL(k_fit_weighted_fold, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const double *)workspace, moments, (int)G);
+    VCY_LAUNCH_CHECK();
+    return VCY_OK;
+}
+
+template <typename T>
+static void fit_fused_launch(const void *Y, const void *X, int fm, const void *S, const void *U, const double *pa, const double *pb,
+                             const double *pc, const double *pd, const double *sa, const double *sb, double pw, const unsigned char *cmask,
+                             void *workspace, int64_t C, int64_t G, int64_t ld, hipStream_t st)
+{
+    dim3 grid((unsigned)((G + 255) / 256), FIT_CB);
+#define VCY_LAUNCH_F(FM, CM)                                                                                                          \
+    hipLaunchKernelGGL((k_moments_fused<T, FM, CM>), grid, dim3(256), 0, st, (const T *)Y, (const T *)X, (const T *)S, (const T *)U, pa, pb, \
+                       pc, pd, sa, sb, pw, (double *)workspace, (int)C, (int)G, ld, cmask)
+#define VCY_LAUNCH_FM(FM) do { if (cmask) { VCY_LAUNCH_F(FM, true); } else { VCY_LAUNCH_F(FM, false); } } while (0)
+    if (fm == 0) VCY_LAUNCH_FM(0); else if (fm == 1) VCY_LAUNCH_FM(1); else if (fm == 2) VCY_LAUNCH_FM(2); else VCY_LAUNCH_FM(3);
+#undef VCY_LAUNCH_FM
+#undef VCY_LAUNCH_F
+}
+
+extern "C" int vcy_fit_weighted_moments_fused(const void *Y, const void *X, int fused_mode, const void *S, const void *U, const double *pa,
+                                              const double *pb, const double *pc, const double *pd, const double *sa, const double *sb,
+                                              double power, const unsigned char *cell_mask, double *moments, void *workspace, int64_t C,
+                                              int64_t G, int64_t ld, int dtype, vcy_stream stream)
+{
+    VCY_REQUIRE(Y && X && S && pa && pb && moments && workspace, "fit_weighted_moments_fused: null pointer");
+    VCY_REQUIRE(C > 0 && G > 0 && ld >= G, "fit_weighted_moments_fused: bad shape");
+    VCY_REQUIRE(dtype == VCY_F32 || dtype == VCY_F64, "fit_weighted_moments_fused: bad dtype");
+    VCY_REQUIRE(fused_mode >= 0 && fused_mode <= 3, "fit_weighted_moments_fused: bad fused_mode");
+    VCY_REQUIRE(fused_mode == 2 || U, "fit_weighted_moments_fused: U needed");
+    VCY_REQUIRE(fused_mode != 3 || (pc && pd && sa && sb), "fit_weighted_moments_fused: maxmin_double needs pc, pd, sa, sb");
+    hipStream_t st = as_stream(stream);
+    if (dtype == VCY_F32) fit_fused_launch<float>(Y, X, fused_mode, S, U, pa, pb, pc, pd, sa, sb, power, cell_mask, workspace, C, G, ld, st);
+    else fit_fused_launch<double>(Y, X, fused_mode, S, U, pa, pb, pc, pd, sa, sb, power, cell_mask, workspace, C, G, ld, st);
+    VCY_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_fit_weighted_fold, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const double *)workspace, moments, (int)G);
     VCY_LAUNCH_CHECK();
     return VCY_OK;

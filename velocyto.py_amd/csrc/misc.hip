@@ -285,17 +285,9 @@ __global__ __launch_bounds__(256) void k_gamma_weights(const T *__restrict__ S, 
         const int g = (int)(t % ld);
         T w = T(0);
         if (g < G) {
-            const double s = (double)S[t];
-            if (mode == 0) w = (T)(s / pa[g] + (double)U[t] / pb[g]);
-            else if (mode == 1) w = (T)((s / pa[g]) * ((double)U[t] / pb[g]));
-            else if (mode == 2) {
-                const double lo = pa[g], hi = pb[g];
-                const double r = (fmin(fmax(s, lo), hi) - lo) / (hi - lo);
-                w = (T)(0.5 * (pow(r, pw) + pow(1.0 - r, pw)));
-            } else {
-                const double z = (double)(T)(S[t] / (T)sa[g] + U[t] / (T)sb[g]);   // same T arithmetic as k_build_z
-                w = (T)(((z <= pa[g] || z >= pb[g]) ? 1.0 : 0.0) + ((s <= pc[g] || s >= pd[g]) ? 1.0 : 0.0));
-            }
+            const bool dbl = mode == 3;          // U may be NULL in mode 2; pc, pd, sa, sb belong to mode 3
+            w = gamma_weight_element<T>(mode, S[t], mode != 2 ? U[t] : T(0), pa[g], pb[g], dbl ? pc[g] : 0.0, dbl ? pd[g] : 0.0,
+                                        dbl ? (T)sa[g] : T(1), dbl ? (T)sb[g] : T(1), pw);
         }
         W[t] = w;
     }

@@ -2463,6 +2463,33 @@ def fit_weighted_moments(Y: CellMatrix, X: CellMatrix, weight_mode: int, W: Opti
     return mom
 
 
+def fit_weighted_moments_fused(Y: CellMatrix, X: CellMatrix, fused_mode: int, S: CellMatrix, U: Optional[CellMatrix], pa, pb, pc=None, pd=None,
+                               sa=None, sb=None, power: float = 15.0, cell_mask=None) -> torch.Tensor:
+    """fit_weighted_moments with the weight of gamma_weights(S, U, fused_mode, pa, pb, pc, pd, sa, sb, power) formed inside the fold
+    (vcy_fit_weighted_moments_fused): the (10, G) fp64 moments of gamma_weights + fit_weighted_moments(weight_mode 0) bit for bit,
+    without the dense W - what a streamed block, which has no third buffer, can afford.  fused_mode: 0 "sum", 1 "prod",
+    2 "maxmin_weighted" (U not read), 3 "maxmin_double".  cell_mask as in fit_weighted_moments."""
+    dev = Y.t.device
+    if fused_mode not in (0, 1, 2, 3):
+        raise ValueError(f"fit_weighted_moments_fused: fused_mode {fused_mode!r} (0 sum, 1 prod, 2 maxmin_weighted, 3 maxmin_double)")
+    for m in (X, S, U):
+        if m is not None and (m.C != Y.C or m.G != Y.G or m.ld != Y.ld or m.dtype != Y.dtype):
+            raise ValueError("fit_weighted_moments_fused: Y, X, S and U must share shape, pitch and dtype")
+    f64 = lambda t: None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous()
+    pa, pb, pc, pd, sa, sb = map(f64, (pa, pb, pc, pd, sa, sb))
+    for v in (pa, pb, pc, pd, sa, sb):
+        if v is not None and v.numel() != Y.G:
+            raise ValueError("fit_weighted_moments_fused: the per-gene vectors must hold one value per gene")
+    mom = torch.empty((10, Y.G), dtype=torch.float64, device=dev)
+    ws = _fit_workspace(Y.G, dev)
+    cm = _cell_mask_u8(cell_mask, Y.C, dev, "fit_weighted_moments_fused")
+    _lib.check(_lib.lib().vcy_fit_weighted_moments_fused(Y.t.data_ptr(), X.t.data_ptr(), int(fused_mode), S.t.data_ptr(),
+                                                         None if U is None else U.t.data_ptr(), _p(pa), _p(pb), _p(pc), _p(pd), _p(sa), _p(sb),
+                                                         float(power), _p(cm), mom.data_ptr(), ws.data_ptr(), Y.C, Y.G, Y.ld, Y.code, _stream()),
+               "fit_weighted_moments_fused")
+    return mom
+
+
 def fit_weighted_from_moments(mom: torch.Tensor, n_cells: int, fit_offset: bool = True, box_q: bool = True, lo_gamma: float = 1e-8,
                               up_gamma_default: float = 20.0, up_gamma=None, q_fixed=None, want_R2: bool = True
                               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:

@@ -35,6 +35,7 @@ from . import distributed as D
 from . import ops
 from .analysis import VelocytoLoom, embedding_shift, fix_correlations, markov_csr, sampling_plan, stage_d_args
 from .ops import CellMatrix
+from .streamed_fit import StreamedFit, check_weights
 
 _MATRICES = ("S", "U", "S_sz", "U_sz", "S_norm", "U_norm", "Sx", "Ux", "Sx_sz", "Ux_sz", "Upred", "velocity", "delta_S", "delta_S_rndm",
              "Sx_sz_t")
@@ -48,7 +49,8 @@ class ShardedLoom:
     exchanged.)
 
     Not covered (NotImplementedError): duplicate cells in the kNN space (a distance of 0: the facade then builds the
-    graph through scipy), the non-default weight modes of fit_gammas, knn_random=False, transform="logratio", hidim="pcs"."""
+    graph through scipy), fit_gammas on anything but the pooled size-normalised matrices or with an array of weights,
+    knn_random=False, transform="logratio", hidim="pcs"."""
 
     def __init__(self, loom_path: Optional[str] = None, pcs=None, ts=None, *, dtype=None, group=None, layers=None) -> None:
         self._dtype = ops.resolve_dtype(dtype)
@@ -285,14 +287,42 @@ class ShardedLoom:
 
     def fit_gammas(self, steady_state_bool=None, use_imputed_data: bool = True, use_size_norm: bool = True, fit_offset: bool = True,
                    fixperc_q: bool = False, weighted: bool = True, weights="maxmin_diag", limit_gamma: bool = False, maxmin_perc=[2, 98],
-                   maxmin_weighted_pow: float = 15) -> None:
-        """analysis.py:1120-1260 with its defaults: the percentiles on gene slices (exact: the facade's kernel on every cell of a
-        gene), the weighted fit as per-rank moments, an all-reduce and the box-constrained solve."""
+                   maxmin_weighted_pow: float = 15, _route: Optional[str] = None) -> None:
+        """analysis.py:1120-1260.  The bare default call: the percentiles on gene slices (exact: the facade's kernel on every cell of a
+        gene), the weighted fit as per-rank moments, an all-reduce and the box-constrained solve.  Every other combination of
+        steady_state_bool (a bool mask over all C cells in the user's order), fit_offset, fixperc_q, weighted, weights (a string),
+        limit_gamma, maxmin_perc and maxmin_weighted_pow: the streamed select (streamed_fit.StreamedFit) with the rank's shard as its
+        one block - integer histograms and the moments all-reduced, no gene-slice exchange; the bytes handed to the all-reduces go to
+        exchange_bytes["fit_select"].  _route="select" sends the default fit down that path too.  Not covered (NotImplementedError):
+        use_imputed_data=False, use_size_norm=False, an array of weights, steady_state_bool as an array of cell indices."""
         t0 = time.perf_counter()
-        if (steady_state_bool is not None or not use_imputed_data or not use_size_norm or not fit_offset or fixperc_q or not weighted
-                or not isinstance(weights, str) or weights != "maxmin_diag" or limit_gamma):
-            raise NotImplementedError("ShardedLoom.fit_gammas covers the default fit (weights='maxmin_diag', fit_offset=True)")
+        if not use_imputed_data or not use_size_norm:
+            raise NotImplementedError("ShardedLoom.fit_gammas covers the pooled size-normalised matrices (use_imputed_data=True, use_size_norm=True)")
+        if isinstance(weights, (np.ndarray, torch.Tensor)) and weighted:
+            raise NotImplementedError("ShardedLoom.fit_gammas: an array of weights is not covered (a weight mode by name is)")
+        if weighted:
+            check_weights(weights)
+        if _route not in (None, "select"):
+            raise ValueError(f"_route={_route!r} (None or \"select\")")
+        ss = None
+        if steady_state_bool is not None and np.ndim(steady_state_bool) != 0:
+            ss = np.asarray(steady_state_bool)
+            if ss.dtype != np.bool_:
+                raise NotImplementedError("ShardedLoom.fit_gammas: steady_state_bool as an array of cell indices is not covered (a bool mask is)")
+            if ss.shape != (self.C,):
+                raise ValueError(f"steady_state_bool must be a boolean mask over the {self.C} cells")
+            if not ss.any():
+                raise ValueError("steady_state_bool selects no cell")
+            if ss.all():
+                ss = None
+        self.steady_state = np.ones(self.C, dtype=bool) if ss is None else ss       # analysis.py:1159-1162, whichever route follows
         perc = [float(p) for p in maxmin_perc]
+        default = (ss is None and fit_offset and not fixperc_q and weighted and weights == "maxmin_diag" and not limit_gamma
+                   and perc == [2.0, 98.0] and float(maxmin_weighted_pow) == 15.0)
+        if _route == "select" or not default:
+            self._fit_gammas_select(ss, fit_offset, fixperc_q, weighted, weights, limit_gamma, perc, maxmin_weighted_pow)
+            self._timed("fit_gammas", t0)
+            return
         gs = self._slices()
         Sx, Ux = self._m["Sx"], self._m["Ux"]
         b0 = gs.bytes_moved
@@ -316,6 +346,24 @@ class ShardedLoom:
         self._gammas_dev, self._q_dev = g, q
         self.gammas, self.q, self.R2 = g.cpu().numpy(), q.cpu().numpy(), R2.cpu().numpy()
         self._timed("fit_gammas", t0)
+
+    def _fit_gammas_select(self, ss, fit_offset, fixperc_q, weighted, weights, limit_gamma, perc, power) -> None:
+        """fit_gammas through StreamedFit: the shard is the one block of every walk."""
+        cmask, n_fit = None, self.C
+        if ss is not None:
+            cmask = torch.from_numpy(ss).to(self.dev)[self._mine].to(torch.uint8).contiguous()      # the rank's cells, in the run's order
+            n_fit = int(ss.sum())
+        fit = StreamedFit(self.G, self.C, self._dtype, self.dev, weighted=weighted, weights=weights, fit_offset=fit_offset, fixperc_q=fixperc_q,
+                          limit_gamma=limit_gamma, maxmin_perc=perc, maxmin_weighted_pow=power, n_fit_cells=n_fit, group=self._group)
+        Sx, Ux = self._m["Sx_sz"], self._m["Ux_sz"]
+        for _ in range(fit.n_walks):
+            fit.add_block(Sx, Ux, cell_mask=cmask)
+            fit.end_walk()
+        g, q, R2 = fit.result()
+        self._fit_thresholds = fit.thresholds
+        self.exchange_bytes["fit_select"] = fit.reduced_bytes if D.active() else 0
+        self._gammas_dev, self._q_dev = g, q
+        self.gammas, self.q, self.R2 = g.cpu().numpy(), q.cpu().numpy(), R2.cpu().numpy()
 
     # ------------------------------------------------------------------ stage C
     def _gene_max(self, M: CellMatrix) -> torch.Tensor:
